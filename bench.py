@@ -3,7 +3,7 @@ Fbank → ConvolutionFrontEnd → Conformer encoder forward on synthetic 16 kHz
 batches of 32 x 15 s per GPU (weak scaling: every rank encodes its own
 batch; no collective on the data path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--d-model 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--d-model 256] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch already resident in HBM:
@@ -11,7 +11,12 @@ fused Fbank kernel (+top_db clamp) → 2 fused ConvBlocks → src Linear →
 12 Conformer layers → final LayerNorm, bf16 MFMA (torch.autocast bf16),
 captured once into a HIP graph and replayed.  Rank 0 prints ONE JSON line.
 
-Also reported (rank 0, N=1 path of the contract):
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step returned (the
+encoder output a caller of the step receives) as DIR/<name>.npy, float32;
+inputs and weights are seeded, so two builds can be compared array for array.
+
+With --full also reported (rank 0, N=1 path of the contract):
   roofline      the dominant kernel (the FFN layer-chain kernel; the other
                 fused encoder kernels are listed beside it): its launches of one step re-issued back to
                 back from a HIP graph on the launch stream and timed with HIP
@@ -46,6 +51,26 @@ _T0 = time.perf_counter()
 def progress(msg):
     """One line per phase on stderr (stdout carries only the JSON line)."""
     print(f"[bench {time.perf_counter() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most this much array data in all (under 64 MB with the headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` ({name: tensor}) as
+    path/<name>.npy in float32.  An output beyond its share of DUMP_BYTES is
+    written as a fixed sample: its flattened elements at sorted indices drawn
+    without replacement by numpy's default_rng(0) (the same indices every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // (4 * max(1, len(arrays)))  # elements per array
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        progress(f"wrote {name}.npy {a.shape} to {path}")
 
 
 def build_model(d_model, dev, layers=12):
@@ -424,10 +449,25 @@ def run_c2(args, world, rank, dev):
     # timed region is not the first milliseconds of a cold clock (20 steps
     # timed 0.22 ms per step against 0.11 ms over 200, profiles/r04l_c2_host.log)
     steps, warmup = 10 * args.steps, 10 * args.warmup
-    elapsed, rank_ms = time_steps(step, steps, warmup, world, dev)
+    elapsed, rank_ms, last = time_steps(step, steps, warmup, world, dev)
     ms_per_step = 1000.0 * elapsed / steps
     value = world * args.batch * SECONDS * steps / elapsed
     if rank != 0:
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"features": out if last is None else last})
+    res = {
+        "metric": "audio-sec/sec STFT+Filterbank+Deltas+SpecAugment (16kHz, B=32x15s)",
+        "value": round(value, 1), "unit": "audio-sec/sec", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": round(ms_per_step, 4), "rank_ms_per_step": rank_ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (0.1·N(0,1) 16 kHz)",
+        "config": {"workload": f"C2: Fbank(80) → Δ/ΔΔ (240) → SpecAugment(recipe, in place), B={args.batch}×15s "
+                               f"per GPU, eager (host mask draws per step)",
+                   "global_batch": world * args.batch, "seq_len": T, "parallelism": f"replicas{world}"},
+    }
+    if not args.full:
+        print(json.dumps(res), flush=True)
         return
     # per-kernel: each op alone, back to back, HIP events on the launch stream.
     # SpecAugment's kernels are timed on one fixed host draw (the op itself):
@@ -492,20 +532,12 @@ def run_c2(args, world, rank, dev):
                      "frac": round(nbytes / (us * 1e-6) / 1e9 / PEAK_HBM_GBS, 4)})
     dom = max(kern, key=lambda k: k["us"])
     kernel_sum_us = sum(k["us"] for k in kern)
-    res = {
-        "metric": "audio-sec/sec STFT+Filterbank+Deltas+SpecAugment (16kHz, B=32x15s)",
-        "value": round(value, 1), "unit": "audio-sec/sec", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": round(ms_per_step, 4), "rank_ms_per_step": rank_ms,
+    res.update({
         "kernel_sum_us": round(kernel_sum_us, 2), "step_over_kernel_sum": round(1000.0 * ms_per_step / kernel_sum_us, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic (0.1·N(0,1) 16 kHz)",
-        "config": {"workload": f"C2: Fbank(80) → Δ/ΔΔ (240) → SpecAugment(recipe, in place), B={args.batch}×15s "
-                               f"per GPU, eager (host mask draws per step)",
-                   "global_batch": world * args.batch, "seq_len": T, "parallelism": f"replicas{world}"},
         "roofline": {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": PEAK_HBM_GBS,
                      "unit": "GB/s", "frac": dom["frac"], "traffic": dom["traffic"],
                      "avg_launch_us": dom["us"], "other_kernels": [k for k in kern if k is not dom]},
-    }
+    })
     if not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline_c2(args.batch)
     print(json.dumps(res), flush=True)
@@ -629,10 +661,29 @@ def run_c5(args, world, rank, dev):
     out = step()
     T = out.shape[0] // args.batch
     run = capture(step, args.no_graph)
-    elapsed, rank_ms = time_steps(run, args.steps, args.warmup, world, dev)
+    elapsed, rank_ms, last = time_steps(run, args.steps, args.warmup, world, dev)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * args.batch * SECONDS * args.steps / elapsed
     if rank != 0:
+        return
+    if args.dump_outputs:  # a graph replay returns nothing: its output is the captured tensor
+        dump_outputs(args.dump_outputs, {"encoder_out": last if last is not None else
+                                         (out if args.no_graph else capture.out)})
+    res = {
+        "metric": "audio-sec/sec wav2vec2 CNN frontend + 24L TransformerEncoder fwd (16kHz, B=32x15s)",
+        "value": round(value, 1), "unit": "audio-sec/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "rank_ms_per_step": rank_ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "mxfp8" if prec == "mxfp8" else "bf16", "data": "synthetic (0.1·N(0,1) 16 kHz, random-init weights)",
+        "config": {"workload": f"C5: W2VLatentExtractor(512ch, 7 conv) → Linear 512→1024 → TransformerEncoder "
+                               f"{C5_LAYERS}L d={C5_D} H={C5_H} ffn={C5_FFN} GELU pre-norm, B={args.batch}×15s per GPU"
+                               + (" (GEMMs MXFP8 e4m3 + E8M0 block scales, attention bf16)" if prec == "mxfp8"
+                                  else " (bf16)"),
+                   "global_batch": world * args.batch, "seq_len": T, "parallelism": f"replicas{world}",
+                   "hip_graph": not args.no_graph},
+    }
+    if not args.full:
+        print(json.dumps(res), flush=True)
         return
     total, _ = c5_flops(args.batch)
     from speechbrain_amd import _enc, _w2v
@@ -657,25 +708,14 @@ def run_c5(args, world, rank, dev):
     dom = max(kern.values(), key=lambda k: k["step_share_ms"])
     peak = PEAK_MXFP8_TFLOPS if (prec == "mxfp8" and dom["kernel"] == "mx_gemm") else PEAK_BF16_TFLOPS
     traffic = load_traffic()
-    res = {
-        "metric": "audio-sec/sec wav2vec2 CNN frontend + 24L TransformerEncoder fwd (16kHz, B=32x15s)",
-        "value": round(value, 1), "unit": "audio-sec/sec", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "rank_ms_per_step": rank_ms,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "mxfp8" if prec == "mxfp8" else "bf16", "data": "synthetic (0.1·N(0,1) 16 kHz, random-init weights)",
-        "config": {"workload": f"C5: W2VLatentExtractor(512ch, 7 conv) → Linear 512→1024 → TransformerEncoder "
-                               f"{C5_LAYERS}L d={C5_D} H={C5_H} ffn={C5_FFN} GELU pre-norm, B={args.batch}×15s per GPU"
-                               + (" (GEMMs MXFP8 e4m3 + E8M0 block scales, attention bf16)" if prec == "mxfp8"
-                                  else " (bf16)"),
-                   "global_batch": world * args.batch, "seq_len": T, "parallelism": f"replicas{world}",
-                   "hip_graph": not args.no_graph},
+    res.update({
         "roofline": {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": peak,
                      "unit": "TFLOP/s", "frac": round(dom["achieved"] / peak, 4),
                      "traffic": traffic.get(dom["kernel"]), "launches_per_step": dom["launches_per_step"],
                      "avg_launch_us": dom["avg_launch_us"], "step_algorithmic_tflop": round(total / 1e12, 4),
                      "step_tflops_achieved": round(total / (ms_per_step * 1e-3) / 1e12, 2),
                      "other_kernels": [k for k in kern.values() if k is not dom]},
-    }
+    })
     if not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline_c5()
     print(json.dumps(res), flush=True)
@@ -693,32 +733,95 @@ def capture(step, no_graph):
     torch.cuda.current_stream().wait_stream(s)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        step()
+        capture.out = step()  # the tensor every replay writes its result into
     torch.cuda.synchronize()
     capture.graphs.append(graph)  # keep the graph (and its memory pool) alive
     return graph.replay
 
 
 capture.graphs = []
+capture.out = None
 
 
 def time_steps(run, steps, warmup, world, dev):
     """W untimed runs, then exactly K timed, bracketed by barrier + synchronize;
-    returns (max-over-ranks seconds, per-rank ms per step)."""
+    returns (max-over-ranks seconds, per-rank ms per step, what the last
+    timed run returned: None for a graph replay)."""
     for _ in range(warmup):
         run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        run()
+        last = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     mine = time.perf_counter() - t0
-    return max_over_ranks(mine, world, dev), [round(1000.0 * t / steps, 4) for t in per_rank(mine, world, dev)]
+    return (max_over_ranks(mine, world, dev), [round(1000.0 * t / steps, 4) for t in per_rank(mine, world, dev)],
+            last)
+
+
+def roofline_c3(args, step, fp32, T_e, ms_per_step):
+    """--full, config 3: the roofline entry of the JSON line (None when no
+    kernel of the timed precision was launched)."""
+    total_flops = encoder_flops(args.batch, T_e, args.d_model)
+    # per-kernel timing: the dominant kernels' launches of one step,
+    # replayed back to back from a HIP graph and timed with HIP events
+    # the calls of the timed precision (bf16 operands, or fp32 ones on the parity path)
+    sel_dt = torch.float32 if fp32 else torch.bfloat16
+    bf = lambda t: t.dtype == sel_dt  # noqa: E731
+    probes = [_LaunchProbe("ffn_chain", _ffn_chain_flops, lambda x, a, *r, **k: bf(a[1])),
+              _LaunchProbe("ffn_proj", _ffn_proj_flops, lambda x, ln0, w1, *a, **k: bf(w1)),
+              _LaunchProbe("ffn", _ffn_flops, lambda x, ln0, w1, *a, **k: bf(w1)),
+              _LaunchProbe("conv_module", _conv_module_flops, lambda x, B, T, ln0, w1p, *a, **k: bf(w1p)),
+              _LaunchProbe("gemm", _gemm_flops, lambda a, w, *r, **k: bf(a)),
+              _LaunchProbe("relpos_attention", _attn_flops, lambda qkv, *a, **k: bf(qkv))]
+    for p in probes:
+        p.__enter__()
+    try:
+        step()
+    finally:
+        for p in probes:
+            p.__exit__()
+    kern = {}
+    labels = (("ffn_kernel<256, 1, true, true> (FFN2 + FFN1 + in_proj layer chain)",
+               "ffn_kernel<256, 1, true, true>"),
+              ("ffn_kernel<256, 1, true, false> (FFN1 + in_proj, layer 0)", "ffn_kernel<256, 1, true, false>"),
+              ("ffn_kernel<256, 1, false, false> (final FFN2 + final LayerNorm)",
+               "ffn_kernel<256, 1, false, false>"),
+              ("conv_module_kernel<true> (out_proj + residual + conv module)", "conv_module_kernel<true>"),
+              ("gemm_kernel<float> (exact-f32 projections, all tiles)" if fp32 else
+               "gemm_kernel<bf16> (projections, all tiles)",
+               "gemm_kernel<float" if fp32 else "gemm_kernel<unsigned short, 64, 64, 64, 2>"),
+              ("relpos_flash_kernel<float> (rel-pos attention, exact f32)" if fp32 else
+               "relpos_flash_dma_kernel (rel-pos attention)",
+               "relpos_flash_kernel<float" if fp32 else "relpos_flash_dma_kernel"))
+    for p, (label, pmc_key) in zip(probes, labels):
+        ms, n, fl = p.replay_time()
+        if n:
+            kern[p.name] = {"kernel": label, "pmc_key": pmc_key, "launches_per_step": n,
+                            "avg_launch_us": round(1000.0 * ms / n, 3),
+                            "achieved": round(fl / (ms * 1e-3) / 1e12, 2),
+                            "step_share_ms": round(ms, 4)}
+    progress("per-kernel launch timing done")
+    if not kern:
+        return None
+    dom = max(kern.values(), key=lambda k: k["step_share_ms"])
+    traffic = load_traffic()
+    peak = PEAK_F32_TFLOPS if fp32 else PEAK_BF16_TFLOPS
+    return {
+        "bound": "mfma", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": peak,
+        "unit": "TFLOP/s", "frac": round(dom["achieved"] / peak, 4),
+        "traffic": None if fp32 else traffic.get(dom["pmc_key"]),
+        "traffic_source": "profiles/pmc_traffic.json (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch)",
+        "launches_per_step": dom["launches_per_step"], "avg_launch_us": dom["avg_launch_us"],
+        "step_algorithmic_tflop": round(total_flops / 1e12, 4),
+        "step_tflops_achieved": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2),
+        "other_kernels": [k for k in kern.values() if k is not dom]}
 
 
 def main():
@@ -729,7 +832,13 @@ def main():
     ap.add_argument("--d-model", type=int, default=256)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel roofline figures (launches re-issued "
+                         "from a HIP graph) and the same-run CPU baseline, and add them to the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 60 MB in all: "
+                         "a fixed seeded sample of a larger output)")
     ap.add_argument("--config", choices=["c2", "c3", "c5"], default="c3",
                     help="c3: Fbank→Conformer (the BASELINE metric, default); c2: feature kernels "
                          "(Fbank, Δ/ΔΔ, SpecAugment); c5: wav2vec2 + 24L TransformerEncoder")
@@ -794,9 +903,10 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -809,49 +919,8 @@ def main():
     value = audio / elapsed
 
     if rank == 0:
-        total_flops = encoder_flops(args.batch, T_e, args.d_model)
-        # per-kernel timing: the dominant kernels' launches of one step,
-        # replayed back to back from a HIP graph and timed with HIP events
-        # the calls of the timed precision (bf16 operands, or fp32 ones on the parity path)
-        sel_dt = torch.float32 if fp32 else torch.bfloat16
-        bf = lambda t: t.dtype == sel_dt  # noqa: E731
-        probes = [_LaunchProbe("ffn_chain", _ffn_chain_flops, lambda x, a, *r, **k: bf(a[1])),
-                  _LaunchProbe("ffn_proj", _ffn_proj_flops, lambda x, ln0, w1, *a, **k: bf(w1)),
-                  _LaunchProbe("ffn", _ffn_flops, lambda x, ln0, w1, *a, **k: bf(w1)),
-                  _LaunchProbe("conv_module", _conv_module_flops, lambda x, B, T, ln0, w1p, *a, **k: bf(w1p)),
-                  _LaunchProbe("gemm", _gemm_flops, lambda a, w, *r, **k: bf(a)),
-                  _LaunchProbe("relpos_attention", _attn_flops, lambda qkv, *a, **k: bf(qkv))]
-        for p in probes:
-            p.__enter__()
-        try:
-            step()
-        finally:
-            for p in probes:
-                p.__exit__()
-        kern = {}
-        labels = (("ffn_kernel<256, 1, true, true> (FFN2 + FFN1 + in_proj layer chain)",
-                   "ffn_kernel<256, 1, true, true>"),
-                  ("ffn_kernel<256, 1, true, false> (FFN1 + in_proj, layer 0)", "ffn_kernel<256, 1, true, false>"),
-                  ("ffn_kernel<256, 1, false, false> (final FFN2 + final LayerNorm)",
-                   "ffn_kernel<256, 1, false, false>"),
-                  ("conv_module_kernel<true> (out_proj + residual + conv module)", "conv_module_kernel<true>"),
-                  ("gemm_kernel<float> (exact-f32 projections, all tiles)" if fp32 else
-                   "gemm_kernel<bf16> (projections, all tiles)",
-                   "gemm_kernel<float" if fp32 else "gemm_kernel<unsigned short, 64, 64, 64, 2>"),
-                  ("relpos_flash_kernel<float> (rel-pos attention, exact f32)" if fp32 else
-                   "relpos_flash_dma_kernel (rel-pos attention)",
-                   "relpos_flash_kernel<float" if fp32 else "relpos_flash_dma_kernel"))
-        for p, (label, pmc_key) in zip(probes, labels):
-            ms, n, fl = p.replay_time()
-            if n:
-                kern[p.name] = {"kernel": label, "pmc_key": pmc_key, "launches_per_step": n,
-                                "avg_launch_us": round(1000.0 * ms / n, 3),
-                                "achieved": round(fl / (ms * 1e-3) / 1e12, 2),
-                                "step_share_ms": round(ms, 4)}
-        progress("per-kernel launch timing done")
-        dom = max(kern.values(), key=lambda k: k["step_share_ms"]) if kern else None
-        traffic = load_traffic()
-        peak = PEAK_F32_TFLOPS if fp32 else PEAK_BF16_TFLOPS
+        if args.dump_outputs:  # a graph replay returns nothing: its output is the captured tensor
+            dump_outputs(args.dump_outputs, {"encoder_out": out if (graph is not None or last is None) else last})
         res = {
             "metric": "audio-sec/sec Fbank→Conformer fwd (16kHz, B=32×15s) at 1/2/4/8 GPU",
             "value": round(value, 1),
@@ -871,18 +940,11 @@ def main():
                                    (" (fp32: exact-f32 MFMA, the parity path)" if fp32 else ""),
                        "global_batch": world * args.batch, "seq_len": T_e, "parallelism": f"replicas{world}",
                        "hip_graph": graph is not None},
-            "roofline": None if dom is None else {
-                "bound": "mfma", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": peak,
-                "unit": "TFLOP/s", "frac": round(dom["achieved"] / peak, 4),
-                "traffic": None if fp32 else traffic.get(dom["pmc_key"]),
-                "traffic_source": "profiles/pmc_traffic.json (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch)",
-                "launches_per_step": dom["launches_per_step"], "avg_launch_us": dom["avg_launch_us"],
-                "step_algorithmic_tflop": round(total_flops / 1e12, 4),
-                "step_tflops_achieved": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2),
-                "other_kernels": [k for k in kern.values() if k is not dom]},
         }
-        if not args.no_cpu_baseline and world == 1:
-            res["cpu_baseline"] = cpu_baseline(args.d_model)
+        if args.full:
+            res["roofline"] = roofline_c3(args, step, fp32, T_e, ms_per_step)
+            if not args.no_cpu_baseline and world == 1:
+                res["cpu_baseline"] = cpu_baseline(args.d_model)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()
