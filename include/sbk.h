@@ -147,6 +147,41 @@ int sbk_rnnt_backward(const float* x, const int* labels, int B, int T, int U1, i
 int sbk_rnnt_lattice(const int* Tl, const int* Ul, int B, int T, int U1, int loss_mode, int reduction, float* ws,
                      float* out, void* stream);
 
+/* ------------------------------------------------------------- CTC loss */
+
+/* CTC (speechbrain.nnet.losses.ctc_loss, losses.py:245-294, i.e.
+ * torch.nn.functional.ctc_loss with zero_infinity=True): x (B, T, V) fp32
+ * logits (is_logits=1: log-softmax fused) or log-probs, batch first;
+ * targets (B, Lmax) int32 without blanks (entries at j >= tg_len[b] are never
+ * read); in_len, tg_len (B,) int32 absolute lengths on the device.  Computes
+ * the compact log-probs of the 2*L_b+1 extended states, the α and β lattices
+ * and loss[b] = -log P (B floats; 0 for an utterance with no valid alignment,
+ * NaN for lengths outside [0, T] x [0, Lmax] or a label outside [0, V)).
+ * ws: sbk_ctc_workspace_floats(B, T, Lmax) floats, 8-byte aligned, kept for
+ * the backward.  Returns 1002 (before any launch) if 2*Lmax+1 > 3073. */
+int sbk_ctc_forward(const float* x, const int* targets, const int* in_len, const int* tg_len, int B, int T, int V,
+                    int Lmax, int blank, int is_logits, float* ws, float* loss, void* stream);
+long long sbk_ctc_workspace_floats(int B, int T, int Lmax);
+
+/* Dense gradient (B, T, V) from the forward's workspace, rows scaled by
+ * grad_out[b].  is_logits=0: torch's ctc_loss convention wrt the log-probs,
+ * exp(lp) - occupancy (every row sums to 0); is_logits=1: wrt the logits,
+ * softmax - occupancy.  Rows t >= in_len[b] and utterances without a valid
+ * alignment are zero.  Bit-identical from run to run. */
+int sbk_ctc_backward(const float* x, const int* targets, const int* in_len, const int* tg_len, int B, int T, int V,
+                     int Lmax, int blank, int is_logits, const float* ws, const float* grad_out, float* grad,
+                     void* stream);
+
+/* Row kernel of nll_loss / kldiv_loss (losses.py:405-452, 525-594): over the
+ * rows r = b*U + u of x (B, U, V) fp32 with batch stride sb floats,
+ * sel[r] = x[r, targets[r]] (NaN for a target outside [0, V)) and
+ * rsum[r] = sum_v x[r, v]; the backward writes
+ * grad[r, v] = a[r]*[v == targets[r]] + c[r] in the same layout. */
+int sbk_nll_rows_forward(const float* x, const int* targets, int B, int U, long long sb, int V, float* sel,
+                         float* rsum, void* stream);
+int sbk_nll_rows_backward(const int* targets, const float* a, const float* c, int B, int U, long long sb, int V,
+                          float* grad, void* stream);
+
 /* ------------------------------------------------- fused transducer head */
 
 /* Joint ("sum" + nonlinearity, transducer_joint.py:57-95) -> Linear(J -> V,

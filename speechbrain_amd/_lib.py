@@ -105,6 +105,12 @@ SIGNATURES = {
     "sbk_rnnt_workspace_floats": [_i, _i, _i],
     "sbk_logsoftmax_topk": [_vp, _ll, _i, _i, _i, _vp, _vp, _vp],
     "sbk_rnnt_backward": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
+    # ctc.hip (CTC loss, nll / kldiv row kernel)
+    "sbk_ctc_forward": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "sbk_ctc_workspace_floats": [_i, _i, _i],
+    "sbk_ctc_backward": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "sbk_nll_rows_forward": [_vp, _vp, _i, _i, _ll, _i, _vp, _vp, _vp],
+    "sbk_nll_rows_backward": [_vp, _vp, _vp, _i, _i, _ll, _i, _vp, _vp],
     # attention.hip
     "sbk_relpos_attention": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],
@@ -149,7 +155,7 @@ SIGNATURES = {
     "sbk_joint_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "sbk_joint_bwd_workspace_floats": [_i, _i, _i, _i],
 }
-RESTYPES = {"sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong}
+RESTYPES = {"sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong, "sbk_ctc_workspace_floats": ctypes.c_longlong}
 
 _lib = None
 _load_error = None
