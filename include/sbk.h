@@ -327,6 +327,30 @@ int sbk_ffn_chain(const float* x, int M, int D, int d_eff, int H, int act, float
                   float alphab, float* out, const float* gn, const float* bn, float epsn, void* u, int u_bf16,
                   const void* img, long long img_elems, int np, void* yp, void* stream);
 
+/* Weight-stream image of the convolution-module stage of sbk_conv_ffn_chain:
+ * w1p (2D, D) GLU-permuted and w2 (D, D) bf16 as 12 tiles of 256 rows x 64 k
+ * in stream order (8 of w1p: per 64 k, the first then the second GLU group of
+ * every wave; 4 of w2), rows swizzled as in sbk_ffn_image.  D = 256. */
+long long sbk_conv_image_elems(int D);
+int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, void* stream);
+
+/* sbk_conv_module_pre (o, wo required) followed by sbk_ffn_chain with its
+ * projection tail (np > 0) in one launch, one workgroup per 48-frame tile of
+ * one utterance: the convolution module's output rows stay on the CU as the
+ * chain's input and residual.  c* arguments: the convolution module's (as
+ * sbk_conv_module_pre; cimg = sbk_conv_image(w1p, w2)); H .. yp: the chain's
+ * (as sbk_ffn_chain).  out (B*T, D) fp32 receives block B's output and must
+ * not alias x; yp (B*T, np) bf16.  D = 256, K <= 31. */
+int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D, int d_eff,
+                       const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg, long long cimg_elems,
+                       const float* cb1p, const float* wc, const float* bc, int K, int causal, const float* cln1_w,
+                       const float* cln1_b, float ceps1, const float* cb2, const unsigned char* kpm, int H, int act,
+                       float slope, const float* g0, const float* b0, float eps0, const float* b1, const float* b2,
+                       float alpha, const float* gp, const float* bp, float epsp, const float* g0b, const float* b0b,
+                       float eps0b, const float* b1b, const float* b2b, float alphab, float* out, const float* gn,
+                       const float* bn, float epsn, const void* img, long long img_elems, int np, void* yp,
+                       void* stream);
+
 /* LayerNorm (normalization.py:172-223; Conformer.py:178,194,340): one or two
  * chained LayerNorms over rows of x (M, D) fp32, D <= 1024. */
 int sbk_layernorm(const float* x, int M, int D, const float* g1, const float* b1, float eps1, void* out1,

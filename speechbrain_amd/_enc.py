@@ -307,18 +307,23 @@ class _ImageCache:
     def _drop(self, key):
         self._d.pop(key, None)
 
-    def get(self, ws, np_, stream):
+    @staticmethod
+    def _build_ffn(ws, np_, stream):
+        w1, w2, w1b, w2b, wp = ws
+        D, H = w1.shape[1], w1.shape[0]
+        n = int(lib().sbk_ffn_image_elems(D, H, np_, int(w1b is not None)))
+        if n <= 0:
+            raise SbkError(f"sbk_ffn_image_elems: unsupported shape D={D} H={H} np={np_}")
+        img = torch.empty(n, device=w1.device, dtype=_bf16)
+        check(lib().sbk_ffn_image(ptr(w1), ptr(w2), ptr(w1b), ptr(w2b), ptr(wp), D, H, np_, ptr(img),
+                                  ctypes.c_void_p(stream.cuda_stream)), "sbk_ffn_image")
+        return img
+
+    def get(self, ws, np_, stream, build=None):
         key = tuple((w.data_ptr(), w._version) if w is not None else None for w in ws) + (np_,)
         hit = self._d.pop(key, None)
         if hit is None:
-            w1, w2, w1b, w2b, wp = ws
-            D, H = w1.shape[1], w1.shape[0]
-            n = int(lib().sbk_ffn_image_elems(D, H, np_, int(w1b is not None)))
-            if n <= 0:
-                raise SbkError(f"sbk_ffn_image_elems: unsupported shape D={D} H={H} np={np_}")
-            img = torch.empty(n, device=w1.device, dtype=_bf16)
-            check(lib().sbk_ffn_image(ptr(w1), ptr(w2), ptr(w1b), ptr(w2b), ptr(wp), D, H, np_, ptr(img),
-                                      ctypes.c_void_p(stream.cuda_stream)), "sbk_ffn_image")
+            img = (build or self._build_ffn)(ws, np_, stream)
             ev = torch.cuda.Event()
             ev.record(stream)
             refs = tuple(weakref.ref(w, lambda _r, k=key: self._drop(k)) for w in ws if w is not None)
@@ -342,6 +347,29 @@ def ffn_image(w1, w2, w1b=None, w2b=None, wp=None):
             raise TypeError("ffn_image: contiguous bf16 weights")
     img = _FFN_IMAGES.get((w1, w2, w1b, w2b, wp), 0 if wp is None else wp.shape[0], torch.cuda.current_stream(w1.device))
     return img
+
+
+_CONV_IMAGES = _ImageCache()
+
+
+def _build_conv_image(ws, np_, stream):
+    w1p, w2 = ws
+    D = w2.shape[0]
+    n = int(lib().sbk_conv_image_elems(D))
+    if n <= 0 or tuple(w1p.shape) != (2 * D, D) or tuple(w2.shape) != (D, D):
+        raise SbkError(f"sbk_conv_image: unsupported shapes {tuple(w1p.shape)}, {tuple(w2.shape)}")
+    img = torch.empty(n, device=w1p.device, dtype=_bf16)
+    check(lib().sbk_conv_image(ptr(w1p), ptr(w2), D, ptr(img), ctypes.c_void_p(stream.cuda_stream)), "sbk_conv_image")
+    return img
+
+
+def conv_image(w1p, w2):
+    """The weight-stream image of the convolution-module stage of
+    conv_ffn_chain (w1p (2D, D) GLU-permuted, w2 (D, D), bf16)."""
+    for t in (w1p, w2):
+        if t.dtype != _bf16 or not t.is_contiguous():
+            raise TypeError("conv_image: contiguous bf16 weights")
+    return _CONV_IMAGES.get((w1p, w2), 0, torch.cuda.current_stream(w1p.device), build=_build_conv_image)
 
 
 @custom_op("sbk::ffn", mutates_args=())
@@ -447,6 +475,78 @@ def ffn_chain(x, a, b, act, slope, next_ln, wp, deff=None):
                                    a[4], float(a[5]), gp, bp, float(ep), b[0][0], b[0][1], float(b[0][2]), b[1], b[2],
                                    b[3], b[4], float(b[5]), next_ln[0], next_ln[1], float(next_ln[2]), wp,
                          int(deff or x.shape[1]))
+
+
+@custom_op("sbk::conv_ffn_chain", mutates_args=())
+def _conv_ffn_chain_op(x: torch.Tensor, B: int, T: int, o: torch.Tensor, wo: torch.Tensor, bo: Optional[torch.Tensor],
+                       cg0: torch.Tensor, cb0: torch.Tensor, ce0: float, w1p: torch.Tensor, b1p: torch.Tensor,
+                       wc: torch.Tensor, bc: Optional[torch.Tensor], causal: bool, cg1: torch.Tensor,
+                       cb1: torch.Tensor, ce1: float, cw2: torch.Tensor, cb2: Optional[torch.Tensor],
+                       kpm: Optional[torch.Tensor], act: int, slope: float, g0: torch.Tensor, b0: torch.Tensor,
+                       e0: float, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, alpha: float,
+                       gp: Optional[torch.Tensor], bp: Optional[torch.Tensor], ep: float, g0b: torch.Tensor,
+                       b0b: torch.Tensor, e0b: float, w1b: torch.Tensor, b1b: torch.Tensor, w2b: torch.Tensor,
+                       b2b: torch.Tensor, alphab: float, gn: torch.Tensor, bn: torch.Tensor, en: float,
+                       wp: torch.Tensor, deff: int) -> tuple[torch.Tensor, torch.Tensor]:
+    M, NP = x.shape[0], wp.shape[0]
+    if M != B * T:
+        raise ValueError(f"conv_ffn_chain: x has {M} rows, B * T = {B * T}")
+    out = torch.empty_like(x)
+    y = torch.empty(M, NP, device=x.device, dtype=_bf16)
+    _conv_ffn_chain_into(out, y, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, causal, cg1, cb1, ce1, cw2, cb2,
+                         kpm, act, slope, g0, b0, e0, w1, b1, w2, b2, alpha, gp, bp, ep, g0b, b0b, e0b, w1b, b1b, w2b,
+                         b2b, alphab, gn, bn, en, wp, deff)
+    return out, y
+
+
+def _conv_ffn_chain_into(out, y, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, causal, cg1, cb1, ce1, cw2, cb2,
+                         kpm, act, slope, g0, b0, e0, w1, b1, w2, b2, alpha, gp, bp, ep, g0b, b0b, e0b, w1b, b1b, w2b,
+                         b2b, alphab, gn, bn, en, wp, deff):
+    """The launch of sbk::conv_ffn_chain into caller-owned out (>= B*T rows of
+    D fp32) and y (>= B*T rows of NP bf16)."""
+    D = x.shape[1]
+    H, NP = w1.shape[0], wp.shape[0]
+    cimg = conv_image(w1p, cw2)
+    img = ffn_image(w1, w2, w1b, w2b, wp)
+    rc = lib().sbk_conv_ffn_chain(ptr(x), ptr(o), ptr(wo), ptr(bo), B, T, D, deff, ptr(cg0), ptr(cb0), float(ce0),
+                                  ptr(cimg), cimg.numel(), ptr(b1p), ptr(wc), ptr(bc), wc.shape[0], int(causal),
+                                  ptr(cg1), ptr(cb1), float(ce1), ptr(cb2), ptr(kpm), H, act, float(slope), ptr(g0),
+                                  ptr(b0), float(e0), ptr(b1), ptr(b2), float(alpha), ptr(gp), ptr(bp), float(ep),
+                                  ptr(g0b), ptr(b0b), float(e0b), ptr(b1b), ptr(b2b), float(alphab), ptr(out), ptr(gn),
+                                  ptr(bn), float(en), ptr(img), img.numel(), NP, ptr(y), stream_of(x))
+    check(rc, "sbk_conv_ffn_chain")
+
+
+@_conv_ffn_chain_op.register_fake
+def _(x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, causal, cg1, cb1, ce1, cw2, cb2, kpm, act, slope, g0, b0,
+      e0, w1, b1, w2, b2, alpha, gp, bp, ep, g0b, b0b, e0b, w1b, b1b, w2b, b2b, alphab, gn, bn, en, wp, deff):
+    return torch.empty_like(x), x.new_empty((x.shape[0], wp.shape[0]), dtype=_bf16)
+
+
+def conv_ffn_chain_supported(D, K, H, NP):
+    """Shapes the fused conv-module + layer-chain launch takes (the chain's LDS
+    at H = 2048 leaves no room for it)."""
+    return conv_module_supported(D, K) and ffn_proj_supported(D, H, NP) and H <= 1024
+
+
+def conv_ffn_chain(x, B, T, pre, conv, kpm, a, b, act, slope, next_ln, wp, deff=None):
+    """conv_module(x, ..., pre=pre) followed by ffn_chain(., a, b, ...) in one
+    launch: the convolution module's output rows stay on chip.  pre = (o, wo,
+    bo); conv = (ln0, w1p, b1p, wc, bc, causal, ln1, w2, b2) as conv_module's
+    arguments; a, b, next_ln, wp as ffn_chain's.  Returns (b's output fp32,
+    next_ln(out) · wp^T bf16)."""
+    o, wo, bo = pre
+    cln0, w1p, b1p, wc, bc, causal, cln1, cw2, cb2 = conv
+    require_device(x, o, wo, w1p, cw2, a[1], b[1], wp)
+    if b[1].shape != a[1].shape or b[3].shape != a[3].shape:
+        raise ValueError(f"conv_ffn_chain: block shapes differ ({tuple(a[1].shape)}/{tuple(a[3].shape)} vs "
+                         f"{tuple(b[1].shape)}/{tuple(b[3].shape)})")
+    gp, bp, ep = a[6] if a[6] is not None else (None, None, 0.0)
+    return OPS.conv_ffn_chain(x, int(B), int(T), o, wo, bo, cln0[0], cln0[1], float(cln0[2]), w1p, b1p, wc, bc,
+                              bool(causal), cln1[0], cln1[1], float(cln1[2]), cw2, cb2, kpm, ACT[act], float(slope),
+                              a[0][0], a[0][1], float(a[0][2]), a[1], a[2], a[3], a[4], float(a[5]), gp, bp, float(ep),
+                              b[0][0], b[0][1], float(b[0][2]), b[1], b[2], b[3], b[4], float(b[5]), next_ln[0],
+                              next_ln[1], float(next_ln[2]), wp, int(deff or x.shape[1]))
 
 
 def ffn(x, ln0, w1, b1, act, slope, w2, b2, alpha, post_ln=None, next_ln=None, next_dtype=_bf16, out=None, deff=None):

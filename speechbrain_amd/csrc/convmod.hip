@@ -45,6 +45,10 @@
 // at once: ~15k cycles to the last wave's data) and phase 1 at ~22 B/clk of
 // weights with every wave re-reading all 80 U rows from LDS (LDS bound:
 // 144 KB of LDS traffic per K-slice).
+// Round 7: layers 0 .. n-2 of the chained encoder run these phases as the
+// prologue of the layer-chain kernel (convstage.h, 8 waves, an image-fed
+// 2-slot weight ring); this kernel serves the last layer and every caller of
+// sbk_conv_module / sbk_conv_module_pre.
 #include "mfma.h"
 
 using namespace sbk;

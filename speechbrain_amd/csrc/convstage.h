@@ -1,0 +1,490 @@
+// The Conformer convolution module as a stage of the layer-chain kernel
+// (ffn.hip: conv_chain_kernel), included there inside its namespace.
+//
+// The arithmetic and its rounding points are those of convmod.hip's
+// conv_module_kernel<true> (phase -1 .. phase 3, see its header); the thread
+// map is the chain's: 8 waves at up to 256 VGPRs instead of 16 at 128, so
+// that one register budget serves both and phase 3's accumulators land in
+// the chain's residual layout — wave w, lane (g, fr): rows mt*16 + fr, units
+// (w*2 + j)*16 + 4g + e — and never leave the CU.
+//   phase -1: wave w owns 32 out_proj units (two 16-unit tiles) of the 80
+//             staged frames; wo fragments straight from global (L2);
+//   phase 1 : wave w owns GLU groups 2w and 2w + 1 (64 permuted rows of
+//             W1p): the U fragments of a K-step are read once per 64 weight
+//             rows instead of once per 32;
+//   phase 2a: thread (channel, half) slides its window over 24 frames;
+//   phase 2b: one wave per frame, 6 frames per wave;
+//   phase 3 : wave w: units (w*2 + j)*16, three 16-frame m-tiles.
+// Phases 1 and 3 stream their weights as the chain does: a pre-tiled,
+// pre-swizzled image in stream order (sbk_conv_image: 8 tiles of W1p, 4 of
+// W2, 256 rows x 64 k each, ffn_image_kernel's row swizzle), a wave's share of
+// a tile one contiguous 4 KB run, through a 2-slot ring (one tile in flight
+// behind the one being read) in the buffers the phase does not use.
+#pragma once
+
+struct ConvStageArgs {
+  const float* x;  // (B*T, D) fp32 residual stream
+  int B, T, K, padL;
+  const float *g0, *b0;  // LN0
+  float eps0;
+  const bf16_t* img;  // sbk_conv_image(w1p, w2)
+  const float* b1;    // (2D) permuted like w1p
+  const float* wc;    // (K, D) depthwise taps, tap-major
+  const float* bc;    // (D) or null
+  const float *g1, *b1n;  // LN1
+  float eps1;
+  const float* b2;      // (D) or null
+  const uint8_t* kpm;   // (B*T) padding mask or null
+  const bf16_t* o;      // (B*T, D) attention output
+  const bf16_t* wo;     // (D, D) out_proj weight (row-major)
+  const float* bo;      // (D) or null
+};
+
+constexpr int CS_D = 256, CS_BM = FFN_BM, CS_KMAX = 31;
+constexpr int CS_ROWS = 80;  // staged frames (BM + K - 1 <= 78, padded to 5 m-tiles)
+constexpr int CS_MT1 = CS_ROWS / 16, CS_MT3 = CS_BM / 16;
+constexpr int CS_NW = FFN_NW, CS_NT = FFN_NT;
+constexpr int CS_S = CS_D + FFN_PAD;  // U / G row stride: rows swizzled by ffn_sw, as Xn / Hs
+constexpr int CS_TILE = 256 * 64;     // elements of an image tile
+constexpr int CS_P1T = 8, CS_P3T = 4; // image tiles of phase 1 (4 K-steps x 2 group halves) and phase 3
+// LDS (bytes): U/V, G, the fp32 conv tile; ring slot 0 over G, slot 1 over the conv tile's front
+constexpr int CS_OFF_G = CS_ROWS * CS_S * 2, CS_OFF_CV = 2 * CS_OFF_G;
+constexpr int CS_LDS = CS_OFF_CV + CS_BM * CS_D * 4;
+static_assert(CS_TILE * 2 <= CS_OFF_G && CS_TILE * 2 <= CS_BM * CS_D * 4, "ring slots fit");
+
+// wave w's 4 KB of an image tile -> its 4 KB of a ring slot, four 1-KB LDS-DMA
+// pieces from one base (the instruction offset applies to both addresses).
+// From inline asm: the compiler sees no LDS write in flight, so the stage's
+// plain LDS accesses get no alias-guard waits, and the ring waits are
+// explicit counted vmcnt.  (m0 is written here and by the chain's DMA builtin
+// only, each right before its use.)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void cs_issue(const bf16_t* img, int tile, bf16_t* slot, int w, int lane) {
+  const bf16_t* src = img + (long long)tile * CS_TILE + w * 2048 + lane * 8;
+  const uint32_t la = __builtin_amdgcn_readfirstlane(lds_addr(slot + w * 2048));
+  asm volatile(
+      "s_mov_b32 m0, %1\n\ts_nop 0\n\t"
+      "global_load_lds_dwordx4 %0, off\n\t"
+      "global_load_lds_dwordx4 %0, off offset:1024\n\t"
+      "global_load_lds_dwordx4 %0, off offset:2048\n\t"
+      "global_load_lds_dwordx4 %0, off offset:3072" ::"v"(src),
+      "s"(la)
+      : "memory", "m0");
+}
+#pragma clang diagnostic pop
+// fragment of slot row `row`, 16-B chunk c (8 consecutive k)
+__device__ __forceinline__ bf16x8 cs_frag(const bf16_t* slot, int row, int c) {
+  return *reinterpret_cast<const bf16x8*>(slot + row * 64 + ((c ^ ((row >> 1) & 7)) << 3));
+}
+__device__ __forceinline__ int cs_gldu8(const uint8_t* p) {
+  int v;
+  asm volatile("global_load_ubyte %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+__device__ __forceinline__ void cs_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// One tile (frames t0 .. t0 + 47 of utterance b) of the convolution module on
+// x + o wo^T + bo.  zres[j][mt]: the module's output rows in the chain's
+// residual layout, zero for frames at or past T.  `stage()` runs once before
+// the first workgroup barrier (the caller's own LDS staging, outside
+// [0, CS_LDS)).
+template <typename F>
+__device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, float npad, unsigned char* smem, int b,
+                                           int t0, f32x4 (&zres)[2][CS_MT3], F&& stage) {
+  bf16_t* Us = reinterpret_cast<bf16_t*>(smem);           // CS_ROWS x CS_S (U, later V)
+  bf16_t* Gs = reinterpret_cast<bf16_t*>(smem + CS_OFF_G);  // CS_ROWS x CS_S
+  float* Cv = reinterpret_cast<float*>(smem + CS_OFF_CV);   // CS_BM x CS_D fp32 conv output
+  bf16_t* slot[2] = {Gs, reinterpret_cast<bf16_t*>(Cv)};
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fr = lane & 15, g = lane >> 4, fk = 8 * g;
+  const int fks = fk ^ ffn_sw(fr);
+  const int f0 = t0 - a.padL;  // frame of staged row 0
+  const int nrows = CS_BM + a.K - 1;
+  const long long ubase = (long long)b * a.T;
+
+  // ---- phase -1: x_att = x + o wo^T + bo over the staged frames, LN0 -> U
+  float4 xres[2][CS_MT3];
+  {
+    constexpr int OC = CS_ROWS * (CS_D / 8) / CS_NT;  // 16-B o chunks per thread
+    static_assert(OC * CS_NT == CS_ROWS * (CS_D / 8), "whole chunks");
+    uint4 ov[OC];
+#pragma unroll
+    for (int i = 0; i < OC; ++i) {
+      const int c = tid + i * CS_NT;
+      const int r = c / (CS_D / 8), ch = c - r * (CS_D / 8);
+      const int fc = min(max(f0 + r, 0), a.T - 1);
+      ov[i] = *reinterpret_cast<const uint4*>(a.o + (ubase + fc) * CS_D + ch * 8);
+    }
+    // LN0's scratch (partials, statistics, affine) sits past ring slot 1
+    float* lnscr = Cv + CS_TILE / 2;
+    constexpr int RS = CS_NW + 4;  // partial-row stride (floats), 16-B aligned
+    static_assert(CS_TILE / 2 + 2 * CS_ROWS * RS + 2 * CS_ROWS + 2 * CS_D <= CS_BM * CS_D, "LN0 scratch fits");
+    float* gb0s = lnscr + 2 * CS_ROWS * RS + 2 * CS_ROWS;  // [g0 | b0]
+    const float4 gbv = tid < CS_D / 2 ? *reinterpret_cast<const float4*>((tid < CS_D / 4 ? a.g0 : a.b0) +
+                                                                         4 * (tid % (CS_D / 4)))
+                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+    // wave w: units (w*2 + j)*16 .. +15 of all CS_MT1 frame tiles; D[unit 4g + e][frame mt*16 + fr]
+    float4 xv[2][CS_MT1], bo4[2];
+    bf16x8 fwo[2][CS_D / 32];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int u0 = (w * 2 + j) * 16 + 4 * g;
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) {
+        const int f = min(max(f0 + mt * 16 + fr, 0), a.T - 1);
+        xv[j][mt] = *reinterpret_cast<const float4*>(a.x + (ubase + f) * CS_D + u0);
+      }
+      bo4[j] = a.bo ? *reinterpret_cast<const float4*>(a.bo + u0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const bf16_t* wrowo = a.wo + (long long)((w * 2 + j) * 16 + fr) * CS_D + fk;
+#pragma unroll
+      for (int kk = 0; kk < CS_D / 32; ++kk) fwo[j][kk] = ld8(wrowo + kk * 32);
+    }
+#pragma unroll
+    for (int i = 0; i < OC; ++i) {
+      const int c = tid + i * CS_NT;
+      const int r = c / (CS_D / 8), ch = c - r * (CS_D / 8), f = f0 + r;
+      const bool live = r < nrows && f >= 0 && f < a.T;
+      *reinterpret_cast<uint4*>(Gs + r * CS_S + ((ch * 8) ^ ffn_sw(r))) = live ? ov[i] : uint4{0u, 0u, 0u, 0u};
+    }
+    if (tid < CS_D / 2) *reinterpret_cast<float4*>(gb0s + 4 * tid) = gbv;
+    stage();
+    cs_barrier();
+    f32x4 acc[2][CS_MT1];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) acc[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < CS_D / 32; ++kk)
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) {
+        const bf16x8 fo = *reinterpret_cast<const bf16x8*>(Gs + (mt * 16 + fr) * CS_S + kk * 32 + fks);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[j][mt] = FFN_MFMA(fwo[j][kk], fo, acc[j][mt]);
+      }
+    float xa[2][CS_MT1][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) {
+        xa[j][mt][0] = xv[j][mt].x + (acc[j][mt][0] + bo4[j].x);
+        xa[j][mt][1] = xv[j][mt].y + (acc[j][mt][1] + bo4[j].y);
+        xa[j][mt][2] = xv[j][mt].z + (acc[j][mt][2] + bo4[j].z);
+        xa[j][mt][3] = xv[j][mt].w + (acc[j][mt][3] + bo4[j].w);
+      }
+    // phase 3's residual: output frame mt*16 + fr is staged row mt*16 + fr +
+    // padL, held (same units) by lane (fr + padL) % 16 of tile (mt*16 + fr +
+    // padL) / 16: two lane permutes per value and a select
+    {
+      const int q = a.padL >> 4, rr = a.padL & 15;  // q <= 1 (K <= 31)
+      const int src = ((lane & 0x30) + ((fr + rr) & 15)) << 2;
+      const bool hi = fr + rr >= 16;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int mt = 0; mt < CS_MT3; ++mt) {
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float lo_v = q == 0 ? xa[j][mt][e] : xa[j][mt + 1][e];
+            const float hi_v = q == 0 ? xa[j][mt + 1][e] : xa[j][mt + 2][e];
+            const float lo = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(lo_v)));
+            const float hv = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(hi_v)));
+            v[e] = hi ? hv : lo;
+          }
+          xres[j][mt] = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    }
+    // LN0 over the 256 units of each frame: 8 per lane, 4 lanes per wave
+    // (col4), 8 waves through LDS; sum and sum of squares in one exchange
+    // (var = E[x^2] - mean^2 in fp32, as conv_module_kernel<true>)
+    float* red = lnscr;  // [CS_ROWS][RS] sums, then [CS_ROWS][RS] squares
+#pragma unroll
+    for (int mt = 0; mt < CS_MT1; ++mt) {
+      float s = 0.f, q2 = 0.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        s += (xa[j][mt][0] + xa[j][mt][1]) + (xa[j][mt][2] + xa[j][mt][3]);
+        q2 += (xa[j][mt][0] * xa[j][mt][0] + xa[j][mt][1] * xa[j][mt][1]) +
+              (xa[j][mt][2] * xa[j][mt][2] + xa[j][mt][3] * xa[j][mt][3]);
+      }
+      const float ps = col4_sum(s), pq = col4_sum(q2);
+      if (g == 0) {
+        red[(mt * 16 + fr) * RS + w] = ps;
+        red[CS_ROWS * RS + (mt * 16 + fr) * RS + w] = pq;
+      }
+    }
+    cs_barrier();
+    // every wave is past its reads of Gs: phase 1's first two tiles land
+    // under the statistics exchange and the LN0 application
+    cs_issue(a.img, 0, slot[0], w, lane);
+    cs_issue(a.img, 1, slot[1], w, lane);
+    float* stat = red + 2 * CS_ROWS * RS;  // [CS_ROWS] mean, [CS_ROWS] rstd
+    if (w < (CS_ROWS + 63) / 64 && w * 64 + lane < CS_ROWS) {
+      const int row = w * 64 + lane;
+      float t = 0.f, t2 = 0.f;
+#pragma unroll
+      for (int k4 = 0; k4 < CS_NW / 4; ++k4) {
+        const float4 a4 = *reinterpret_cast<const float4*>(red + row * RS + 4 * k4);
+        const float4 q4 = *reinterpret_cast<const float4*>(red + CS_ROWS * RS + row * RS + 4 * k4);
+        t += a4.x; t += a4.y; t += a4.z; t += a4.w;
+        t2 += q4.x; t2 += q4.y; t2 += q4.z; t2 += q4.w;
+      }
+      const float mu = t * inv_n;  // padded channels are zero: they add nothing to t or t2
+      stat[row] = mu;
+      stat[CS_ROWS + row] = 1.0f / sqrtf(fmaxf(t2 * inv_n - mu * mu, 0.f) + a.eps0);
+    }
+    cs_barrier();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int u0 = (w * 2 + j) * 16 + 4 * g;
+      const float4 g04 = *reinterpret_cast<const float4*>(gb0s + u0);
+      const float4 b04 = *reinterpret_cast<const float4*>(gb0s + CS_D + u0);
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) {
+        const float mean = stat[mt * 16 + fr], rstd = stat[CS_ROWS + mt * 16 + fr];
+        const int r = mt * 16 + fr, f = f0 + r;
+        const bool live = r < nrows && f >= 0 && f < a.T;
+        uint2 pk = make_uint2(0u, 0u);
+        if (live) {
+          pk.x = pack_bf16x2((xa[j][mt][0] - mean) * rstd * g04.x + b04.x, (xa[j][mt][1] - mean) * rstd * g04.y + b04.y);
+          pk.y = pack_bf16x2((xa[j][mt][2] - mean) * rstd * g04.z + b04.z, (xa[j][mt][3] - mean) * rstd * g04.w + b04.w);
+        }
+        *reinterpret_cast<uint2*>(Us + r * CS_S + (u0 ^ ffn_sw(fr))) = pk;
+      }
+    }
+  }
+  cs_barrier();
+
+  // ---- phase 1: G = GLU(U W1p^T + b1p) over CS_ROWS frames.  Tile q = K-step
+  // q / 2, half q % 2: wave w's rows of it are GLU group 2w + q % 2 (16 value
+  // rows, 16 gate rows)
+  {
+    f32x4 acc[2][2][CS_MT1];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int mt = 0; mt < CS_MT1; ++mt) acc[h][t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bf16x8 fa[2][CS_MT1];  // U fragments of the K-step, shared by its two tiles
+#pragma unroll
+    for (int q = 0; q < CS_P1T; ++q) {
+      const int kt = q >> 1, h = q & 1;
+      // this tile landed; the one issued after it stays in flight
+      if (q + 1 < CS_P1T)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      bf16x8 fw[2][2];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) fw[ks][t] = cs_frag(slot[q & 1], w * 32 + t * 16 + fr, ks * 4 + g);
+      if (h == 0) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int mt = 0; mt < CS_MT1; ++mt)
+            fa[ks][mt] = *reinterpret_cast<const bf16x8*>(Us + (mt * 16 + fr) * CS_S + kt * 64 + ks * 32 + fks);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (q + 2 < CS_P1T) cs_issue(a.img, q + 2, slot[q & 1], w, lane);  // the slot's fragments are in VGPRs
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int mt = 0; mt < CS_MT1; ++mt) acc[h][t][mt] = FFN_MFMA(fw[ks][t], fa[ks][mt], acc[h][t][mt]);
+    }
+    cs_barrier();  // every wave's ring reads are done before G overwrites Gs
+    // GLU epilogue: lane holds frames mt*16 + fr, units 4g..4g+3 of each
+    // tile; tiles (0, 1) = (value, gate) of channel group 2w + h
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int ch = (w * 2 + h) * 16 + 4 * g;            // output channels ch .. ch + 3
+      const int pa = (w * 2 + h) * 32 + 4 * g, pg = pa + 16;  // permuted rows of value / gate
+      const float4 ba = *reinterpret_cast<const float4*>(a.b1 + pa);
+      const float4 bg = *reinterpret_cast<const float4*>(a.b1 + pg);
+      const float bav[4] = {ba.x, ba.y, ba.z, ba.w}, bgv[4] = {bg.x, bg.y, bg.z, bg.w};
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) {
+        const int r = mt * 16 + fr, f = f0 + r;
+        const bool live = r < nrows && f >= 0 && f < a.T;
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float va = acc[h][0][mt][e] + bav[e], vg = acc[h][1][mt][e] + bgv[e];
+          const float sg = va * __builtin_amdgcn_rcpf(1.0f + __expf(-vg));  // bf16 output: approx rcp
+          o[e] = live ? sg : 0.f;
+        }
+        uint2 pk;
+        pk.x = pack_bf16x2(o[0], o[1]);
+        pk.y = pack_bf16x2(o[2], o[3]);
+        *reinterpret_cast<uint2*>(Gs + r * CS_S + (ch ^ ffn_sw(fr))) = pk;
+      }
+    }
+  }
+  cs_barrier();
+
+  // ---- phase 2a: depthwise conv, thread (channel c, half h) over 24 frames,
+  // two taps per v_dot2 (bf16 operands, fp32 accumulation) -> fp32 tile
+  {
+    const int c = tid & (CS_D - 1), h = tid >> 8;
+    constexpr int NF = CS_BM / (CS_NT / CS_D);
+    constexpr int NP = (CS_KMAX + 1) / 2;  // tap pairs (tap 31 is zero)
+    float wk[2 * NP];
+#pragma unroll
+    for (int k = 0; k < 2 * NP; ++k) {  // (K, D): coalesced; clamped address + select
+      const float v = a.wc[min(k, a.K - 1) * CS_D + c];
+      wk[k] = k < a.K ? v : 0.f;
+    }
+    const float bias = a.bc ? a.bc[c] : 0.f;
+    static_assert((CS_NT / CS_D - 1) * NF + NF + 2 * NP - 1 <= CS_ROWS, "every window row is staged");
+    static_assert(NF % 4 == 0, "h * NF keeps bits 0-1 of the row; frame pairs");
+    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+    bf2 tp[NP], ev[NF / 2 + NP - 1], od[NF / 2 + NP - 1];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      tp[j] = __builtin_bit_cast(bf2, pack_bf16x2(wk[2 * j], wk[2 * j + 1]));
+      asm volatile("" : "+v"(tp[j]));
+    }
+    // row h * NF + k: its swizzle is ffn_sw(k) ^ ffn_sw(h * NF)
+    const int cx = c ^ ffn_sw(h * NF);
+    const unsigned short* Gu0 = reinterpret_cast<const unsigned short*>(Gs) + h * NF * CS_S + cx;
+    const unsigned short* Gu1 = reinterpret_cast<const unsigned short*>(Gs) + h * NF * CS_S + (cx ^ 8);
+    auto gu = [&](int k) __attribute__((always_inline)) { return (uint32_t)(ffn_sw(k) ? Gu1 : Gu0)[k * CS_S]; };
+    uint32_t g0 = gu(0);
+#pragma unroll
+    for (int r = 0; r < NF / 2 + NP - 1; ++r) {
+      const uint32_t g1 = gu(2 * r + 1), g2 = gu(2 * r + 2);
+      ev[r] = __builtin_bit_cast(bf2, g0 | (g1 << 16));
+      od[r] = __builtin_bit_cast(bf2, g1 | (g2 << 16));
+      g0 = g2;
+    }
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      float s = bias;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) s = __builtin_amdgcn_fdot2_f32_bf16(tp[j], (i & 1) ? od[i / 2 + j] : ev[i / 2 + j], s, false);
+      Cv[(h * NF + i) * CS_D + c] = s;
+    }
+  }
+  cs_barrier();
+
+  // ---- phase 2b: LN1 -> Swish -> V (over U), one wave per frame, 4 channels
+  // per lane.  Gs is free: phase 3's first tile lands under this phase (the
+  // LN1 affine and phase 3's bias / key-padding bytes are loaded first and
+  // waited for by count, ahead of it)
+  f32x4 bb2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  int km[CS_MT3] = {};
+  {
+    f32x4 g14 = gld4(a.g1 + lane * 4), b14 = gld4(a.b1n + lane * 4);
+    // unconditional (a null b2 / kpm reads g1 instead and is zeroed after the
+    // wait): a load under a branch would be merged with the zero by a
+    // register copy the compiler places before the data has landed
+    const float* b2p = a.b2 ? a.b2 : a.g1;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bb2[j] = gld4(b2p + (w * 2 + j) * 16 + 4 * g);
+#pragma unroll
+    for (int mt = 0; mt < CS_MT3; ++mt)
+      km[mt] = cs_gldu8(a.kpm ? a.kpm + ubase + min(t0 + mt * 16 + fr, a.T - 1) : reinterpret_cast<const uint8_t*>(a.g1));
+    cs_issue(a.img, CS_P1T, slot[0], w, lane);
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    vtie(g14);
+    vtie(b14);
+    vtie(bb2[0]);
+    vtie(bb2[1]);
+#pragma unroll
+    for (int mt = 0; mt < CS_MT3; ++mt) asm volatile("" : "+v"(km[mt]));
+    if (!a.b2) bb2[0] = bb2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!a.kpm) km[0] = km[1] = km[2] = 0;
+    const float gm[4] = {g14[0], g14[1], g14[2], g14[3]}, bt[4] = {b14[0], b14[1], b14[2], b14[3]};
+    constexpr int FPW = CS_BM / CS_NW;  // frames per wave, side by side: their reduction chains interleave
+    float v[FPW][4], mean[FPW], rstd[FPW];
+#pragma unroll
+    for (int u = 0; u < FPW; ++u) {
+      const float4 v4 = *reinterpret_cast<const float4*>(Cv + (w + u * CS_NW) * CS_D + lane * 4);
+      v[u][0] = v4.x; v[u][1] = v4.y; v[u][2] = v4.z; v[u][3] = v4.w;
+    }
+#pragma unroll
+    for (int u = 0; u < FPW; ++u) mean[u] = wave_sum_v((v[u][0] + v[u][1]) + (v[u][2] + v[u][3])) * inv_n;
+#pragma unroll
+    for (int u = 0; u < FPW; ++u) {
+      float q = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) q += (v[u][e] - mean[u]) * (v[u][e] - mean[u]);
+      rstd[u] = q;
+    }
+#pragma unroll
+    for (int u = 0; u < FPW; ++u)
+      rstd[u] = 1.0f / sqrtf((wave_sum_v(rstd[u]) - npad * mean[u] * mean[u]) * inv_n + a.eps1);
+#pragma unroll
+    for (int u = 0; u < FPW; ++u) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float z = (v[u][e] - mean[u]) * rstd[u] * gm[e] + bt[e];
+        v[u][e] = z * __builtin_amdgcn_rcpf(1.0f + __expf(-z));  // bf16 output (as the GLU above)
+      }
+      uint2 pk;
+      pk.x = pack_bf16x2(v[u][0], v[u][1]);
+      pk.y = pack_bf16x2(v[u][2], v[u][3]);
+      *reinterpret_cast<uint2*>(Us + (w + u * CS_NW) * CS_S + ((lane * 4) ^ ffn_sw(w))) = pk;  // CS_NW % 8 == 0
+    }
+  }
+  cs_barrier();
+
+  // ---- phase 3: z = x_att + rowmask0(V W2^T + b2), kept in registers
+  {
+    f32x4 acc[2][CS_MT3];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int mt = 0; mt < CS_MT3; ++mt) acc[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    cs_issue(a.img, CS_P1T + 1, slot[1], w, lane);  // the conv tile is free: the LN1 statistics are read
+#pragma unroll
+    for (int kt = 0; kt < CS_P3T; ++kt) {
+      if (kt + 1 < CS_P3T)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      bf16x8 fw[2][2], fa[2][CS_MT3];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) fw[ks][j] = cs_frag(slot[kt & 1], w * 32 + j * 16 + fr, ks * 4 + g);
+#pragma unroll
+        for (int mt = 0; mt < CS_MT3; ++mt)
+          fa[ks][mt] = *reinterpret_cast<const bf16x8*>(Us + (mt * 16 + fr) * CS_S + kt * 64 + ks * 32 + fks);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (kt + 2 < CS_P3T) cs_issue(a.img, CS_P1T + kt + 2, slot[kt & 1], w, lane);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int mt = 0; mt < CS_MT3; ++mt) acc[j][mt] = FFN_MFMA(fw[ks][j], fa[ks][mt], acc[j][mt]);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int mt = 0; mt < CS_MT3; ++mt) {
+        const bool live = t0 + mt * 16 + fr < a.T;
+        const bool m = km[mt] != 0;
+        const float4 xv = xres[j][mt];
+        f32x4 o;
+        o[0] = xv.x + (m ? 0.f : acc[j][mt][0] + bb2[j][0]);
+        o[1] = xv.y + (m ? 0.f : acc[j][mt][1] + bb2[j][1]);
+        o[2] = xv.z + (m ? 0.f : acc[j][mt][2] + bb2[j][2]);
+        o[3] = xv.w + (m ? 0.f : acc[j][mt][3] + bb2[j][3]);
+        zres[j][mt] = live ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+  }
+}

@@ -66,6 +66,12 @@
 // ~40 B/clk, the per-CU LDS-DMA issue rate (MI355X_MICROARCH ldsdma-fill:
 // 16 KiB per 0.154 us), while its 12 MFMAs per wave fill 384 of them.
 // Fewer weight bytes per CU need more rows per CU than M / 256 = 47.
+// Round 7: conv_chain_kernel runs the convolution module of layer i
+// (convstage.h: conv_module_kernel<true>'s phases on this kernel's 8-wave
+// thread map) as the prologue of the layer chain, on one 48-frame tile of
+// one utterance; the module's output lands in the chain's residual layout
+// and never leaves the CU.  69.9 us per launch against 48.6 (chain) + 28.3
+// (conv module), 85.7 MB of HBM traffic against 110.2.
 #include "mfma.h"
 
 using namespace sbk;
@@ -303,13 +309,17 @@ __device__ __forceinline__ void load_frags(bf16x8 (&xa)[K1][KS][MT], const bf16_
       for (int mt = 0; mt < MT; ++mt) tie(xa[r][ks][mt]);
 }
 
+#include "convstage.h"
 
 // s_memtime timeline of the waves of workgroup 128 (probe builds only)
 SBK_PROBE_BUFFER(g_ffn_tl, 16, 256)
 #define FFN_TL(i) SBK_PROBE(if (tl_rec >= 0 && lane == 0) g_ffn_tl[tl_rec][i] = __builtin_amdgcn_s_memtime();)
 
-template <int D, int ACT, bool PROJ, bool CHAIN>
-__global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
+// The body of ffn_kernel and conv_chain_kernel.  CONV: the workgroup's rows
+// are one 48-frame tile of one utterance and come out of the convolution
+// module (conv_stage) in registers instead of from a.x.
+template <int D, int ACT, bool PROJ, bool CHAIN, bool CONV>
+__device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* cs) {
   constexpr int BM = FFN_BM, HC = 256, NW = FFN_NW, NT = FFN_NT;
   constexpr int XS = D + FFN_PAD, HS = HC + FFN_PAD;   // LDS row strides (elements), +32 B pad: conflict-free b128 reads
   constexpr int MT = BM / 16;                // m-tiles (3)
@@ -337,7 +347,13 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fr = lane & 15, g = lane >> 4, fk = (8 * g) ^ ffn_sw(fr);  // chunk g of the swizzled rows mt*16 + fr
-  const int m0 = blockIdx.x * BM;
+  // rows m0 .. m0 + BM - 1, live below mlim (CONV: the utterance's end, not the flat M)
+  int m0 = blockIdx.x * BM, mlim = a.M;
+  if constexpr (CONV) {
+    const int nblk = (cs->T + BM - 1) / BM, b = blockIdx.x / nblk;
+    m0 = b * cs->T + (blockIdx.x - b * nblk) * BM;
+    mlim = (b + 1) * cs->T;
+  }
   const int NCH = a.H / HC;
   const int S = NCH * SPC;                              // K-steps of one FFN block
   const int SF = CHAIN ? 2 * S : S;                     // FFN K-steps (blocks A, B)
@@ -374,17 +390,72 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
   // tiles instead of being paid again after the last MFMA.
   constexpr int NRW = (BM + NW - 1) / NW;    // LN rows per wave
   f32x4 xres[T][MT];
+  if constexpr (CONV) {
+    // ---- the convolution module in front of block A.  Its LDS ([0, CS_LDS))
+    // lies under the ring, Xn and the hidden-chunk buffers; b1, the reduction
+    // scratch and the parameter rows are past it and are staged while it
+    // runs, and block A's LN0 affine waits in the tail of the second hidden
+    // buffer (free until chunk 1's activation step).
+    static_assert(T == 2 && MT == CS_MT3 && CHAIN && PROJ, "conv_stage hands over the chain's residual layout");
+    float* ga0 = reinterpret_cast<float*>(smem + CS_LDS);  // [g0 | b0] of block A
+    static_assert(CS_LDS + 2 * D * 4 <= (NB * TROWS * BK + BM * XS + 2 * BM * HS) * 2, "LN0 affine below b1");
+    static_assert(CS_LDS >= (NB * TROWS * BK + BM * XS + BM * HS) * 2, "LN0 affine in the second hidden buffer");
+    const float* psrc = w == P_B2 ? a.b2 : w == P_GP ? a.gp : w == P_BP ? a.bp : w == P_G0B ? a.g0b
+                      : w == P_B0B ? a.b0b : w == P_B2B ? a.b2b : w == P_GN ? a.gn : a.bn;
+    const bool b1t = tid * 4 < a.H;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 pv = z4, b1v = z4, b1bv = z4, gav = z4;
+    if (psrc) pv = *reinterpret_cast<const float4*>(psrc + lane * PER);
+    if (b1t) {
+      b1v = *reinterpret_cast<const float4*>(a.b1 + tid * 4);
+      b1bv = *reinterpret_cast<const float4*>(a.b1b + tid * 4);
+    }
+    if (tid < D / 2) gav = *reinterpret_cast<const float4*>((tid < D / 4 ? a.g0 : a.b0) + 4 * (tid % (D / 4)));
+    const int nblk = (cs->T + BM - 1) / BM, ub = blockIdx.x / nblk;
+    conv_stage(*cs, a.inv_n, a.npad, smem, ub, (blockIdx.x - ub * nblk) * BM, xres, [&]() __attribute__((always_inline)) {
+      if (psrc) *reinterpret_cast<float4*>(prm + w * D + lane * PER) = pv;
+      if (b1t) {
+        *reinterpret_cast<float4*>(b1s + tid * 4) = b1v;
+        *reinterpret_cast<float4*>(b1s + a.H + tid * 4) = b1bv;
+      }
+      if (tid < D / 2) *reinterpret_cast<float4*>(ga0 + 4 * tid) = gav;
+    });
+    // every wave is done with V and the conv ring: block A's first two tiles
+    // land under its LN0 (the conv module's output rows are A's residual)
+    lds_barrier();
+    issue(0, 0);
+    issue(1, 1);
+    float z[T][MT][4];
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z[j][mt][e] = xres[j][mt][e];
+    row_ln<D, T, MT, NW>(z, red, ga0, ga0 + D, a.eps0, w, g, fr, a.inv_n, a.npad);
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+      const int d = (w * T + j) * 16 + 4 * g;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        uint2 pk;
+        pk.x = pack_bf16x2(z[j][mt][0], z[j][mt][1]);
+        pk.y = pack_bf16x2(z[j][mt][2], z[j][mt][3]);
+        lds_st2(Xn + (mt * 16 + fr) * XS + (d ^ ffn_sw(fr)), pk);
+      }
+    }
+  } else {
 #pragma unroll
   for (int j = 0; j < T; ++j)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      const int row = min(m0 + mt * 16 + fr, a.M - 1);
+      const int row = min(m0 + mt * 16 + fr, mlim - 1);
       xres[j][mt] = gld4(a.x + (long long)row * D + (w * T + j) * 16 + 4 * g);
     }
   f32x4 xv[NRW];
 #pragma unroll
   for (int i = 0; i < NRW; ++i) {
-    const int rr = w + i * NW, row = min(m0 + rr, a.M - 1);
+    const int rr = w + i * NW, row = min(m0 + rr, mlim - 1);
     xv[i] = gld4(a.x + (long long)row * D + lane * PER);
   }
   f32x4 g04 = gld4(a.g0 + lane * PER), b04 = gld4(a.b0 + lane * PER);
@@ -417,7 +488,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
   for (int i = 0; i < NRW; ++i) {
     const int rr = w + i * NW;
     if (rr >= BM) break;
-    const bool live = m0 + rr < a.M;
+    const bool live = m0 + rr < mlim;
     const float v[4] = {live ? xv[i][0] : 0.f, live ? xv[i][1] : 0.f, live ? xv[i][2] : 0.f, live ? xv[i][3] : 0.f};
     const float mean = wave_sum_v(v[0] + v[1] + v[2] + v[3]) * a.inv_n;
     float q = 0.f;
@@ -433,6 +504,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
   if (psrc) lds_st4(prm + w * D + lane * PER, pv);
   if (b1t) lds_st4(b1s + tid * 4, b1v);
   if (CHAIN && b1t) lds_st4(b1s + a.H + tid * 4, b1bv);
+  }  // !CONV
 
   f32x4 acc1[T][MT], acc2[T][MT];
 #pragma unroll
@@ -655,7 +727,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
     // past ST-1.
     static_assert(MT <= K1, "stores of a column block fit in its steps");
     const int ncp = a.np / TROWS;
-    const bool full = m0 + BM <= a.M;
+    const bool full = m0 + BM <= mlim;
     uint2 yq[T][MT];  // the previous column block's y (bf16)
     for (int nc = 0; nc < ncp; ++nc) {
 #pragma unroll
@@ -729,7 +801,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
           yq[t][mt].y = pack_bf16x2(v[2], v[3]);
           acc1[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
           const int row = m0 + mt * 16 + (ln & 15);
-          if ((!full || nc == ncp - 1) && row < a.M)
+          if ((!full || nc == ncp - 1) && row < mlim)
             *reinterpret_cast<uint2*>(a.yp + (long long)row * a.np + nc * TROWS + w * (T * 16) + t * 16 + 4 * (ln >> 4)) =
                 yq[t][mt];
         }
@@ -747,7 +819,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           const int row = m0 + mt * 16 + fr;
-          if (row < a.M) *reinterpret_cast<f32x4*>(a.out + (long long)row * D + (w * T + j) * 16 + 4 * g) = ov[j][mt];
+          if (row < mlim) *reinterpret_cast<f32x4*>(a.out + (long long)row * D + (w * T + j) * 16 + 4 * g) = ov[j][mt];
         }
     }
     SBK_PROBE(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)  // the end mark includes the store drain
@@ -761,7 +833,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const int row = m0 + mt * 16 + fr;
-      if (row < a.M)
+      if (row < mlim)
         *reinterpret_cast<float4*>(a.out + (long long)row * D + d) =
             make_float4(z[j][mt][0], z[j][mt][1], z[j][mt][2], z[j][mt][3]);
     }
@@ -774,7 +846,7 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const int row = m0 + mt * 16 + fr;
-        if (row >= a.M) continue;
+        if (row >= mlim) continue;
         if (a.u_bf16) {
           uint2 pk;
           pk.x = pack_bf16x2(z[j][mt][0], z[j][mt][1]);
@@ -788,6 +860,19 @@ __global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
     }
   }
   FFN_TL(196);
+}
+
+template <int D, int ACT, bool PROJ, bool CHAIN>
+__global__ void __launch_bounds__(FFN_NT) ffn_kernel(FfnArgs a) {
+  ffn_body<D, ACT, PROJ, CHAIN, false>(a, nullptr);
+}
+
+// [out_proj + residual + conv module of layer i] + [FFN2 + norm2 of layer i,
+// FFN1 + norm1 + in_proj of layer i+1] on one 48-frame tile of one utterance:
+// the conv module's output rows never leave the CU.  Grid: B * ceil(T / 48).
+template <int ACT>
+__global__ void __launch_bounds__(FFN_NT) conv_chain_kernel(FfnArgs a, ConvStageArgs c) {
+  ffn_body<256, ACT, true, true, true>(a, &c);
 }
 
 template <int D>
@@ -825,6 +910,43 @@ int ffn_dispatch(const FfnArgs& a, hipStream_t s) {
   const bool proj = a.np > 0, chain = a.g0b != nullptr;
   if (chain) return proj ? launch_ffn<256, true, true>(a, s) : launch_ffn<256, false, true>(a, s);
   return proj ? launch_ffn<256, true, false>(a, s) : launch_ffn<256, false, false>(a, s);
+}
+
+template <int ACT>
+int launch_conv_chain_act(const FfnArgs& a, const ConvStageArgs& c, unsigned grid, size_t lds, hipStream_t s) {
+  if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&conv_chain_kernel<ACT>), lds)) return (int)e;
+  hipLaunchKernelGGL((conv_chain_kernel<ACT>), dim3(grid), dim3(FFN_NT), lds, s, a, c);
+  return 0;
+}
+
+int conv_chain_dispatch(const FfnArgs& a, const ConvStageArgs& c, hipStream_t s) {
+  const size_t lds = ffn_lds<256>(a.H, true);
+  static_assert(CS_LDS + 2 * 256 * 4 <= (2 * 256 * 64 + FFN_BM * (256 + FFN_PAD) * 3) * 2, "the conv stage lies under ring, Xn, Hs");
+  if (lds > 160 * 1024) return SBK_ERR_ARG;
+  const long long grid = (long long)c.B * ((c.T + FFN_BM - 1) / FFN_BM);
+  if (grid > 0x7fffffffLL) return SBK_ERR_ARG;
+  switch (a.act) {
+    case ACT_SWISH: return launch_conv_chain_act<ACT_SWISH>(a, c, (unsigned)grid, lds, s);
+    case ACT_LRELU: return launch_conv_chain_act<ACT_LRELU>(a, c, (unsigned)grid, lds, s);
+    case ACT_GELU: return launch_conv_chain_act<ACT_GELU>(a, c, (unsigned)grid, lds, s);
+    case ACT_NONE: return launch_conv_chain_act<ACT_NONE>(a, c, (unsigned)grid, lds, s);
+    default: return SBK_ERR_ARG;
+  }
+}
+
+// the conv stage's image: tile q < 8 (phase 1, K-step q / 2, half q % 2): row
+// 32w + i = W1p row 64w + 32 (q % 2) + i, k (q / 2)*64 ..; tile 8 + kt (phase
+// 3): W2 rows, k kt*64 ..; the ring's row swizzle as below
+__global__ void __launch_bounds__(256) conv_image_kernel(const bf16_t* __restrict__ w1p, const bf16_t* __restrict__ w2,
+                                                         bf16_t* __restrict__ img) {
+  const int n = (CS_P1T + CS_P3T) * 256 * 8;  // 16-B chunks
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int s = i >> 11, rem = i & 2047, r = rem >> 3, jp = rem & 7;
+    const int j = jp ^ ((r >> 1) & 7);
+    const bf16_t* src = s < CS_P1T ? w1p + (long long)((r >> 5) * 64 + (s & 1) * 32 + (r & 31)) * CS_D + (s >> 1) * 64
+                                   : w2 + (long long)r * CS_D + (s - CS_P1T) * 64;
+    *reinterpret_cast<uint4*>(img + (long long)i * 8) = *reinterpret_cast<const uint4*>(src + 8 * j);
+  }
 }
 
 // ---- the weight-stream image.  Tile s (256 rows x 64 k, 32 KB) in the order
@@ -998,4 +1120,72 @@ SBK_API int sbk_ffn(const float* x, int M, int D, int d_eff, int H, const float*
                     const float* bn, float epsn, void* u, int u_bf16, void* stream) {
   return sbk_ffn_proj(x, M, D, d_eff, H, g0, b0, eps0, img, img_elems, b1, act, slope, b2, alpha, gp, bp, epsp, out, gn, bn,
                       epsn, u, u_bf16, 0, nullptr, stream);
+}
+
+SBK_API long long sbk_conv_image_elems(int D) { return D == CS_D ? (long long)(CS_P1T + CS_P3T) * CS_TILE : -1; }
+
+SBK_API int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, void* stream) {
+  if (D != CS_D || !w1p || !w2 || !img) return SBK_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(w1p) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(img)) & 15)
+    return SBK_ERR_ARG;
+  hipLaunchKernelGGL(conv_image_kernel, dim3((CS_P1T + CS_P3T) * 8), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const bf16_t*>(w1p), reinterpret_cast<const bf16_t*>(w2),
+                     reinterpret_cast<bf16_t*>(img));
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
+// sbk_conv_module_pre followed by sbk_ffn_chain (with the projection tail) in
+// one launch: x_c = x + o wo^T + bo through the convolution module (c*
+// arguments, cimg = sbk_conv_image(w1p, w2c)), then the chain on x_c's rows,
+// which stay on the CU.  out (B*T, D) fp32 must not alias x (neighbouring
+// tiles read x for the conv halo); yp (B*T, np) bf16.
+SBK_API int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D,
+                               int d_eff, const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg,
+                               long long cimg_elems, const float* cb1p, const float* wc, const float* bc, int K,
+                               int causal, const float* cln1_w, const float* cln1_b, float ceps1, const float* cb2,
+                               const unsigned char* kpm, int H, int act, float slope, const float* g0, const float* b0,
+                               float eps0, const float* b1, const float* b2, float alpha, const float* gp,
+                               const float* bp, float epsp, const float* g0b, const float* b0b, float eps0b,
+                               const float* b1b, const float* b2b, float alphab, float* out, const float* gn,
+                               const float* bn, float epsn, const void* img, long long img_elems, int np, void* yp,
+                               void* stream) {
+  if (B <= 0 || T <= 0 || (long long)B * T > 0x7fffffffLL || D != CS_D || K < 1 || K > CS_KMAX || !x || !out ||
+      x == out || d_eff <= 0 || d_eff > D)
+    return SBK_ERR_ARG;
+  if (!o || !wo || !cln0_w || !cln0_b || !cimg || !cb1p || !wc || !cln1_w || !cln1_b) return SBK_ERR_ARG;
+  if (cimg_elems != sbk_conv_image_elems(D)) return SBK_ERR_ARG;
+  if (!g0b || !b0b || !b1b || !b2b || !gn || !bn || !yp || np <= 0) return SBK_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(wo) | reinterpret_cast<uintptr_t>(bo) |
+       reinterpret_cast<uintptr_t>(cln0_w) | reinterpret_cast<uintptr_t>(cln0_b) | reinterpret_cast<uintptr_t>(cimg) |
+       reinterpret_cast<uintptr_t>(cb1p) | reinterpret_cast<uintptr_t>(cln1_w) | reinterpret_cast<uintptr_t>(cln1_b) |
+       reinterpret_cast<uintptr_t>(cb2) | reinterpret_cast<uintptr_t>(g0b) | reinterpret_cast<uintptr_t>(b0b) |
+       reinterpret_cast<uintptr_t>(b1b) | reinterpret_cast<uintptr_t>(b2b)) & 15)
+    return SBK_ERR_ARG;
+  const int M = B * T;
+  if (ffn_check(x, M, D, H, g0, b0, img, img_elems, 1, b1, act, b2, gp, bp, out, gn, bn, nullptr, np, yp))
+    return SBK_ERR_ARG;
+  FfnArgs a;
+  a.inv_n = 1.0f / (float)d_eff; a.npad = (float)(D - d_eff);
+  a.x = x; a.M = M; a.H = H;
+  a.g0 = g0; a.b0 = b0; a.eps0 = eps0;
+  a.img = reinterpret_cast<const bf16_t*>(img); a.b1 = b1; a.act = act; a.slope = slope;
+  a.b2 = b2; a.alpha = alpha;
+  a.gp = gp; a.bp = bp; a.epsp = epsp;
+  a.out = out;
+  a.gn = gn; a.bn = bn; a.epsn = epsn; a.u = nullptr; a.u_bf16 = 1;
+  a.np = np; a.yp = reinterpret_cast<bf16_t*>(yp);
+  a.g0b = g0b; a.b0b = b0b; a.eps0b = eps0b;
+  a.b1b = b1b; a.b2b = b2b; a.alphab = alphab;
+  ConvStageArgs c;
+  c.x = x; c.B = B; c.T = T; c.K = K; c.padL = causal ? K - 1 : (K - 1) / 2;
+  c.g0 = cln0_w; c.b0 = cln0_b; c.eps0 = ceps0;
+  c.img = reinterpret_cast<const bf16_t*>(cimg); c.b1 = cb1p; c.wc = wc; c.bc = bc;
+  c.g1 = cln1_w; c.b1n = cln1_b; c.eps1 = ceps1;
+  c.b2 = cb2; c.kpm = reinterpret_cast<const uint8_t*>(kpm);
+  c.o = reinterpret_cast<const bf16_t*>(o); c.wo = reinterpret_cast<const bf16_t*>(wo); c.bo = bo;
+  const int rc = conv_chain_dispatch(a, c, (hipStream_t)stream);
+  if (rc) return rc;
+  SBK_CHECK_LAUNCH();
+  return 0;
 }

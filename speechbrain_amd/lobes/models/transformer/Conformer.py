@@ -44,6 +44,10 @@ USE_CONV_MODULE_KERNEL = True
 # FFN2 (+ norm2) of layer i and FFN1 (+ norm1 + in_proj) of layer i+1 in one
 # launch (sbk_ffn_chain), the out_proj in the conv module's prologue
 USE_LAYER_CHAIN = True
+# ... and the conv module of layer i in front of that launch
+# (sbk_conv_ffn_chain): its output rows stay on the CU as the chain's input,
+# two launches per layer instead of three
+USE_CONV_CHAIN = True
 # bf16 stacks with d_model < 256 (conformer_small.yaml: 144) on a zero-padded
 # D = 256 copy, so they take the fused kernels (_PaddedEncoder)
 USE_PADDED_SHADOW = True
@@ -132,18 +136,23 @@ class ConvolutionModule(nn.Module):
                 and self.bottleneck[0].bias is not None and isinstance(self.after_conv[1], Swish)
                 and getattr(self.after_conv[1], "beta", 1) == 1)
 
-    def run_fused(self, x2d, B, T, pad_mask_u8=None, pre=None):
-        """x2d + mask(ConvolutionModule(x2d)) in one launch (bf16 MFMA);
-        pre = (o, wo, bo): on x2d + o wo^T + bo (the MHSA out_proj fused in)."""
+    def fused_params(self):
+        """(ln0, w1p, b1p, taps (K, d), conv bias, causal, ln1, w2, b2): the
+        fused kernels' view of this module (_enc.conv_module / conv_ffn_chain)."""
         w1p, b1p, w2 = self.kernel_weights(_bf16)
         ln = self.after_conv[0]
         lin = self.after_conv[2]
         wc = self._wc.get("taps", [self.conv.weight], lambda: self.conv.weight.detach().reshape(
             self.conv.weight.shape[0], -1).t().contiguous())  # (K, d): coalesced tap loads
-        return _enc.conv_module(x2d, B, T, self.ln_params(), w1p, b1p, wc,
-                                self.conv.bias.detach() if self.conv.bias is not None else None, self.causal,
-                                (ln.weight.detach(), ln.bias.detach(), ln.eps), w2,
-                                lin.bias.detach() if lin.bias is not None else None, pad_mask_u8, pre=pre,
+        return (self.ln_params(), w1p, b1p, wc, self.conv.bias.detach() if self.conv.bias is not None else None,
+                self.causal, (ln.weight.detach(), ln.bias.detach(), ln.eps), w2,
+                lin.bias.detach() if lin.bias is not None else None)
+
+    def run_fused(self, x2d, B, T, pad_mask_u8=None, pre=None):
+        """x2d + mask(ConvolutionModule(x2d)) in one launch (bf16 MFMA);
+        pre = (o, wo, bo): on x2d + o wo^T + bo (the MHSA out_proj fused in)."""
+        ln0, w1p, b1p, wc, bc, causal, ln1, w2, b2 = self.fused_params()
+        return _enc.conv_module(x2d, B, T, ln0, w1p, b1p, wc, bc, causal, ln1, w2, b2, pad_mask_u8, pre=pre,
                                 deff=self._deff)
 
     def train_run(self, x2d, B, T, dtype, pad_mask_u8=None, residual=None):
@@ -427,7 +436,9 @@ class ConformerEncoder(nn.Module):
         """The fused stack as 3 launches per layer: [FFN2_i + norm2_i +
         FFN1_{i+1} + norm1_{i+1} + in_proj_{i+1}] (sbk_ffn_chain), attention,
         [out_proj + residual + conv module] (sbk_conv_module_pre); layer 0's
-        FFN1 is sbk_ffn_proj, the last FFN2 carries the closing LayerNorm."""
+        FFN1 is sbk_ffn_proj, the last FFN2 carries the closing LayerNorm.
+        With USE_CONV_CHAIN the conv module of layers 0 .. n-2 runs in front
+        of the chain in the same launch (sbk_conv_ffn_chain): 2 per layer."""
         d = x.shape[1]
         ln = ConformerEncoderLayer._ln
         L = self.layers
@@ -439,16 +450,23 @@ class ConformerEncoder(nn.Module):
             _, attn, pre = layer.mha_layer.attend_heads(None, B, T, pos, kpm_u8, dtype, need_attn,
                                                         pk=pk_all[:, i * d:(i + 1) * d], qkv=qkv)
             attns.append(attn)
-            x = layer.convolution_module.run_fused(x, B, T, kpm_u8, pre=pre)
             f2 = layer.ffn_module2
+            cm = layer.convolution_module
             if i + 1 < len(L):
                 nl = L[i + 1]
                 a = f2[1].chain_block(ln(layer, f2[0]), 0.5, post_ln=ln(layer, layer.norm2.norm))
                 b = nl.ffn_module1[1].chain_block(ln(nl, nl.ffn_module1[0]), 0.5)
                 act, slope = f2[1].act_name()
-                x, qkv = _enc.ffn_chain(x, a, b, act, slope, ln(nl, nl.norm1.norm), nl.mha_layer.fused_in_proj(dtype),
-                                        deff=f2[1]._deff)
+                wp = nl.mha_layer.fused_in_proj(dtype)
+                if USE_CONV_CHAIN and _enc.conv_ffn_chain_supported(d, cm.conv.weight.shape[-1], a[1].shape[0],
+                                                                    wp.shape[0]):
+                    x, qkv = _enc.conv_ffn_chain(x, B, T, pre, cm.fused_params(), kpm_u8, a, b, act, slope,
+                                                 ln(nl, nl.norm1.norm), wp, deff=f2[1]._deff)
+                    continue
+                x = cm.run_fused(x, B, T, kpm_u8, pre=pre)
+                x, qkv = _enc.ffn_chain(x, a, b, act, slope, ln(nl, nl.norm1.norm), wp, deff=f2[1]._deff)
             else:
+                x = cm.run_fused(x, B, T, kpm_u8, pre=pre)
                 fn = self.norm.norm
                 _, y = f2[1].run_fused(x, ln(layer, f2[0]), 0.5, post_ln=ln(layer, layer.norm2.norm),
                                        next_ln=(fn.weight.detach(), fn.bias.detach(), fn.eps), next_dtype=_f32)
