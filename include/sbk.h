@@ -700,6 +700,40 @@ int sbk_mx_quant(const void* x, int in_bf16, long long ldx, int M, int K, uint8_
 int sbk_mx_dequant(const uint8_t* q, long long ldq, const uint8_t* scales, long long ldsq, int M, int K, float* out,
                    void* stream);
 
+/* ------------------------------------------ joint CTC/attention decoding */
+
+/* One step of CTCPrefixScorer.forward_step (decoders/ctc.py:84-243) without
+ * its (T, 2, N, C) state tensor.  N = B*beam rows; x (B, T, V) fp32 masked CTC
+ * log-probs; r_prev (T, 2, N) fp32; psi_prev (N) fp32 or null (0); last_tok
+ * (N) int64, the last token of each row's prefix (null or prefix_len 0: token
+ * 0, as the reference); cand (N, C) int64 with 1 <= C <= V, or null with
+ * C = 0 for all V tokens; last_frame (B) int32 (a negative index counts from
+ * T).  Frames start ... end-1 are walked, 1 <= start <= T, end <= T (start >=
+ * end: no frame), T <= 4096.  out (N, V) = psi - psi_prev: the eos column is
+ * logaddexp(r_prev[last_frame, 0], r_prev[last_frame, 1]), the blank column
+ * and, with cand, every column outside cand are the sentinel -1e20. */
+int sbk_ctc_prefix_step(const float* x, const float* r_prev, const float* psi_prev, const long long* last_tok,
+                        const long long* cand, const int* last_frame, int B, int beam, int T, int V, int C,
+                        int prefix_len, int start, int end, int blank, int eos, float* out, void* stream);
+
+/* CTCPrefixScorer.permute_mem (ctc.py:245-294) from the step's inputs: new
+ * row n continues row parent[n] (in [0, N)) with token[n]; r_new (T, 2, N)
+ * and psi_new (N) are that pair's forward variables and psi, bit for bit
+ * what sbk_ctc_prefix_step scored (one shared device function).  With cand, a
+ * token outside its parent's candidates takes the parent's candidate 0 for
+ * r_new and the sentinel for psi_new. */
+int sbk_ctc_prefix_advance(const float* x, const float* r_prev, const long long* last_tok, const long long* cand,
+                           const int* last_frame, const long long* parent, const long long* token, int B, int beam,
+                           int T, int V, int C, int prefix_len, int start, int end, int blank, int eos, float* r_new,
+                           float* psi_new, void* stream);
+
+/* ctc_greedy_decode (ctc.py:334-376): per frame the argmax over V (lowest
+ * index on a tie) of x (B, T, V) fp32 with element strides sb, st, sv, over
+ * the first lens[b] frames (int32, clipped to [0, T]); repeats merged, blanks
+ * dropped, the rest compacted into tokens (B, T) int32, counts (B) int32. */
+int sbk_ctc_greedy_decode(const float* x, long long sb, long long st, long long sv, const int* lens, int B, int T,
+                          int V, int blank, int* tokens, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

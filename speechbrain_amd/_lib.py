@@ -116,6 +116,11 @@ SIGNATURES = {
     "sbk_ctc_backward": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "sbk_nll_rows_forward": [_vp, _vp, _i, _i, _ll, _i, _vp, _vp, _vp],
     "sbk_nll_rows_backward": [_vp, _vp, _vp, _i, _i, _ll, _i, _vp, _vp],
+    # ctcdec.hip (CTC prefix scorer step / advance, CTC greedy decode)
+    "sbk_ctc_prefix_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "sbk_ctc_prefix_advance": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp,
+                               _vp],
+    "sbk_ctc_greedy_decode": [_vp, _ll, _ll, _ll, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     # attention.hip
     "sbk_relpos_attention": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],
