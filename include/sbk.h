@@ -734,6 +734,34 @@ int sbk_ctc_prefix_advance(const float* x, const float* r_prev, const long long*
 int sbk_ctc_greedy_decode(const float* x, long long sb, long long st, long long sv, const int* lens, int B, int T,
                           int V, int blank, int* tokens, int* counts, void* stream);
 
+/* ---- kvdec.hip: incremental transformer decoding (fp32) ----------------- */
+
+/* One decode step of the decoder's masked self-attention over an append-only
+ * key/value cache.  q, k_new, v_new: (N, E) views with row stride ld floats
+ * (E = H*dh; the three column blocks of one (N, 3E) in_proj output); kc, vc
+ * (cap, N, E) position-major; anc (N, anc_ld) int32 ancestry table, values
+ * clamped to [0, N), anc[n][L-1] = n; out (N, E).  k_new[n] / v_new[n] are
+ * stored into slot [L-1][n] (no other slot is written), then row n attends
+ * positions j < L through kc / vc[j][anc[n][j]]: exact softmax, scale
+ * 1/sqrt(dh), head h = columns [h*dh, (h+1)*dh).  Needs dh % 4 == 0,
+ * dh <= 128, L <= cap, ld >= E, ld % 4 == 0, anc_ld >= L, 16-byte aligned
+ * float pointers. */
+int sbk_kv_decode_self_attn(const float* q, const float* k_new, const float* v_new, long long ld, float* kc,
+                            float* vc, int cap, const int* anc, long long anc_ld, int N, int H, int dh, int L,
+                            float* out, void* stream);
+
+/* One decode step of the decoder's cross-attention.  q (N, E) with row stride
+ * q_ld; k, v (B, S, E) with row stride kv_ld (the two column blocks of one
+ * (B*S, 2E) projection), B = N / group; row n attends utterance n / group,
+ * keys j < klen[n] (int32, clamped to 1 .. S; null: all S keys).  out (N, E);
+ * probs (N, H, S) or null, 0 at j >= klen.  A workgroup serves one
+ * (utterance, head) and reads each K / V row once for up to 16 of its beams.
+ * Needs dh % 4 == 0, dh <= 128, N % group == 0, strides >= E and % 4 == 0,
+ * 16-byte aligned q / k / v.  Any S (online softmax over 256-key chunks). */
+int sbk_kv_decode_cross_attn(const float* q, long long q_ld, const float* k, const float* v, long long kv_ld,
+                             const int* klen, int N, int group, int H, int dh, int S, float* out, float* probs,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

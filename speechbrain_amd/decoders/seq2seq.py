@@ -19,12 +19,18 @@ What runs where:
     once per step (the reference reads once per row).
 Not carried over, both RNN-searcher features that the reference itself
 mishandles for the transformer's 3-D attention map: using_max_attn_shift and
-coverage_penalty raise NotImplementedError.  A key/value cache for the
-decoder is out of scope: like the reference, every step re-decodes the whole
-prefix.
+coverage_penalty raise NotImplementedError.
+Incremental decoding: with S2STransformerBeamSearch.USE_KV_CACHE set (class or
+instance attribute; off by default) and a decoder that
+TransformerASR.decode_step_supported() takes, a step runs decode_step — the
+newest token only, against a key/value cache and cross-attention K / V
+projected once for the un-inflated utterances (csrc/kvdec.hip) — and a beam
+permutation moves the cache's (N, L) ancestry table, not the cache.  Otherwise,
+like the reference, every step re-decodes the whole prefix.
 """
 import torch
 
+from .. import _kvdec  # noqa: F401  (registers the decode-step ops the cached search runs)
 from .ctc import CTCPrefixScorer
 
 
@@ -307,6 +313,10 @@ def _update_mem(inp_tokens, memory):
 class S2STransformerBeamSearch(S2SBeamSearcher):
     """seq2seq.py:1334-1398.  modules = [TransformerASR, seq_lin, ctc_lin]."""
 
+    # incremental decoding through TransformerASR.decode_step; the constructor
+    # is the reference's, so this is an attribute (as Conformer.USE_CONV_CHAIN)
+    USE_KV_CACHE = False
+
     def __init__(self, modules, temperature=1.0, temperature_lm=1.0, **kwargs):
         super().__init__(**kwargs)
         self.model = modules[0]
@@ -322,13 +332,26 @@ class S2STransformerBeamSearch(S2SBeamSearcher):
     def reset_lm_mem(self, batch_size, device):
         return None
 
+    def _kv_cache(self):
+        return self.USE_KV_CACHE and self.model.decode_step_supported()
+
     def permute_mem(self, memory, index):
+        if self._kv_cache():
+            return memory.permute(index)
         return torch.index_select(memory, dim=0, index=index)
 
     def permute_lm_mem(self, memory, index):
         return torch.index_select(memory, dim=0, index=index)
 
     def forward_step(self, inp_tokens, memory, enc_states, enc_lens):
+        if self._kv_cache():
+            # memory is the decode state: enc_states arrives inflated, every
+            # beam_size-th row is one utterance
+            if memory is None:
+                memory = self.model.init_decode_state(enc_states[::self.beam_size], group=self.beam_size)
+            pred, attn = self.model.decode_step(inp_tokens, memory)
+            prob_dist = self.softmax(self.fc(pred) / self.temperature)
+            return prob_dist[:, -1, :], memory, attn
         memory = _update_mem(inp_tokens, memory)
         pred, attn = self.model.decode(memory, enc_states)
         prob_dist = self.softmax(self.fc(pred) / self.temperature)

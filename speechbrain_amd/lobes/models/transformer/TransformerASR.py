@@ -29,6 +29,8 @@ import torch.nn as nn
 
 from .... import _autograd as A
 from .... import _enc
+from .... import _kvdec
+from ...._lib import require_device
 from ....nnet.activations import Swish
 from ....nnet.attention import RelPosEncXL
 from ....nnet.linear import Linear
@@ -184,6 +186,111 @@ class TransformerASR(nn.Module):
         prediction, self_attns, multihead_attns = self.decoder(tgt, encoder_out, tgt_mask=tgt_mask,
                                                                memory_key_padding_mask=src_key_padding_mask)
         return prediction, multihead_attns[-1]
+
+    # ------------------------------------------------ incremental decoding
+    def decode_step_supported(self):
+        """decode_step's kernels (csrc/kvdec.hip) take this decoder: head size
+        a multiple of 4 up to 128, and both attentions of every layer in the
+        default projection layout (bias, kdim = vdim = d_model, no bias_kv /
+        zero_attn)."""
+        if not hasattr(self, "decoder"):
+            return False
+        for layer in self.decoder.layers:
+            for att in (layer.self_attn, layer.mutihead_attn):
+                a = att.att
+                dh = att.d_model // att.nhead
+                if (dh % 4 or dh > _kvdec.SELF_DH_MAX or not a._qkv_same_embed_dim or a.bias_k is not None
+                        or a.add_zero_attn or a.in_proj_bias is None):
+                    return False
+        return True
+
+    def _decoder_pe(self):
+        """The sine table decode() adds to the target embeddings, (max_len, d)."""
+        if self.attention_type == "RelPosMHAXL":
+            return self.positional_encoding_decoder.pe[0]
+        if self.positional_encoding_type == "fixed_abs_sine":
+            return self.positional_encoding.pe[0]
+        raise ValueError("TransformerASR(positional_encoding=None, attention_type='regularMHA'): the reference "
+                         "leaves the positional embeddings unset here (TransformerASR.py:304-315)")
+
+    @torch.no_grad()
+    def init_decode_state(self, encoder_out, enc_len=None, group=1):
+        """The state of decode_step for encoder_out (B, S, d_model), NOT
+        inflated by the beam: decode_step's rows are N = B·group, row n
+        decoding utterance n // group.  Computes every decoder layer's
+        cross-attention K and V here, once (one GEMM per layer over the
+        [k | v] rows of in_proj); enc_len (B) absolute lengths masks the keys
+        j ≥ enc_len, as decode() does."""
+        require_device(encoder_out)
+        if not self.decode_step_supported():
+            raise NotImplementedError("TransformerASR.decode_step: this decoder is not on the incremental path "
+                                      "(see decode_step_supported); use decode()")
+        B, S, E = encoder_out.shape
+        dtype = _enc.compute_dtype()
+        mem = encoder_out.detach().float()
+        if self.attention_type == "RelPosMHAXL":
+            mem = mem + self.positional_encoding_decoder(mem)
+        mem = mem.reshape(B * S, E)
+        cross_kv = []
+        for layer in self.decoder.layers:
+            ca = layer.mutihead_attn
+            kv = A.linear(mem, ca.att.in_proj_weight[E:], ca.att.in_proj_bias[E:], dtype, ca._wc, "kv_kv",
+                          out_dtype=_f32)
+            cross_kv.append(kv.view(B, S, 2 * E))
+        klen = None
+        if enc_len is not None:
+            klen = enc_len.to(device=encoder_out.device, dtype=torch.int32).repeat_interleave(group).contiguous()
+        return _kvdec.DecodeState(cross_kv, klen, int(group), self.decoder.layers[0].nhead)
+
+    @torch.no_grad()
+    def decode_step(self, tokens, state):
+        """One incremental step of decode(): tokens (N,) — the newest token of
+        every row — → (prediction (N, 1, d_model), attn (N, 1, S)), equal to
+        decode(prefixes, inflated encoder_out)[..., -1:, :] of the rows'
+        prefixes.  Per layer, in TransformerDecoderLayer.forward's order:
+        LayerNorm → one in_proj GEMM (N × 3E) → sbk_kv_decode_self_attn over
+        the cache → out_proj (+ residual); LayerNorm → q GEMM →
+        sbk_kv_decode_cross_attn over the state's K / V → out_proj
+        (+ residual); the FFN; then the decoder's closing LayerNorm.  attn is
+        the last layer's cross-attention weights averaged over the heads.
+        Nothing is read back to the host."""
+        require_device(tokens)
+        dec = self.decoder
+        N, E, H = state.rows, state.d_model, state.nhead
+        if tokens.shape != (N,):
+            raise ValueError(f"decode_step: tokens {tuple(tokens.shape)} != ({N},) rows of the state")
+        pe = self._decoder_pe()
+        if state.steps >= pe.shape[0]:
+            raise ValueError(f"decode_step: position {state.steps} is beyond the sine table ({pe.shape[0]})")
+        dtype = _enc.compute_dtype()
+        x = self.custom_tgt_module(tokens.unsqueeze(1))[:, 0] + pe[state.steps]
+        L = state.begin_step()
+        probs = None
+        last = len(dec.layers) - 1
+        for i, layer in enumerate(dec.layers):
+            pre = layer.normalize_before
+            sa, ca = layer.self_attn, layer.mutihead_attn
+            u = layer.norm1(x) if pre else x
+            qkv = A.linear(u, sa.att.in_proj_weight, sa.att.in_proj_bias, dtype, sa._wc, "kv_in", out_dtype=_f32)
+            o = _kvdec.kv_decode_self_attn(qkv, state.kc[i], state.vc[i], state.anc, H, L)
+            x = A.linear(o, sa.att.out_proj.weight, sa.att.out_proj.bias, dtype, sa._wc, "g_out", res=x)
+            if not pre:
+                x = layer.norm1(x)
+            u = layer.norm2(x) if pre else x
+            q = A.linear(u, ca.att.in_proj_weight[:E], ca.att.in_proj_bias[:E], dtype, ca._wc, "g_q", out_dtype=_f32)
+            o, p = _kvdec.kv_decode_cross_attn(q, state.cross_kv[i], state.klen, state.group, H, i == last)
+            if i == last:
+                probs = p
+            x = A.linear(o, ca.att.out_proj.weight, ca.att.out_proj.bias, dtype, ca._wc, "g_out", res=x)
+            if not pre:
+                x = layer.norm2(x)
+            u = layer.norm3(x) if pre else x
+            x = layer.pos_ffn.run(_enc.to_compute(u, dtype), dtype, residual=x)
+            if not pre:
+                x = layer.norm3(x)
+        x = dec.norm(x)
+        state.steps = L
+        return x.unsqueeze(1), probs.mean(dim=1).unsqueeze(1)
 
     def key_padding_mask(self, T, wav_len, device):
         """TransformerASR.py:295-301: arange(T) > floor(wav_len·T) (uint8)."""
