@@ -351,6 +351,40 @@ int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const floa
                        const float* bn, float epsn, const void* img, long long img_elems, int np, void* yp,
                        void* stream);
 
+/* sbk_conv_module_pre (o, wo required) followed by sbk_ffn with its post-LN
+ * and next-LN in one launch, the end of the encoder stack: the last layer's
+ * convolution module, FFN2 + norm2 (g0 .. epsp) and the encoder's closing
+ * LayerNorm (gn, bn; Conformer.py:340).  Same grid and arguments as
+ * sbk_conv_ffn_chain without block B and the projection; img =
+ * sbk_ffn_image(w1, w2).  Only u (B*T, D) fp32 = LNn(LNp(z)) is written (the
+ * module's output and the pre-LN rows stay on the CU); u must not alias x. */
+int sbk_conv_ffn_tail(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D, int d_eff,
+                      const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg, long long cimg_elems,
+                      const float* cb1p, const float* wc, const float* bc, int K, int causal, const float* cln1_w,
+                      const float* cln1_b, float ceps1, const float* cb2, const unsigned char* kpm, int H, int act,
+                      float slope, const float* g0, const float* b0, float eps0, const float* b1, const float* b2,
+                      float alpha, const float* gp, const float* bp, float epsp, const float* gn, const float* bn,
+                      float epsn, float* u, const void* img, long long img_elems, void* stream);
+
+/* Weight-stream image of the source Linear of sbk_src_ffn_proj: ws (256, Kin)
+ * bf16 as Kin / 64 tiles of 256 rows x 64 k in K order, rows swizzled as in
+ * sbk_ffn_image.  Kin % 64 == 0, Kin <= 768 (-1 / SBK_ERR_ARG otherwise). */
+long long sbk_src_image_elems(int Kin);
+int sbk_src_image(const void* ws, int Kin, void* img, void* stream);
+
+/* sbk_gemm (x = a ws^T + sbias: the src Linear of TransformerASR.py:169-182,
+ * a (M, Kin) bf16, simg = sbk_src_image(ws), sbias (256) fp32 or null)
+ * followed by sbk_ffn_proj on x in one launch; x never reaches memory.  With
+ * rel_len (B floats; M == B * T) the launch also writes the key-padding mask
+ * kpm_out (M bytes) exactly as sbk_length_mask; rel_len null: no mask.  M ..
+ * yp: as sbk_ffn_proj (np > 0); out must not alias a.  D = 256. */
+int sbk_src_ffn_proj(const void* a, int Kin, const void* simg, long long simg_elems, const float* sbias,
+                     const float* rel_len, int T, unsigned char* kpm_out, int M, int D, int d_eff, int H,
+                     const float* g0, const float* b0, float eps0, const void* img, long long img_elems,
+                     const float* b1, int act, float slope, const float* b2, float alpha, const float* gp,
+                     const float* bp, float epsp, float* out, const float* gn, const float* bn, float epsn, int np,
+                     void* yp, void* stream);
+
 /* LayerNorm (normalization.py:172-223; Conformer.py:178,194,340): one or two
  * chained LayerNorms over rows of x (M, D) fp32, D <= 1024. */
 int sbk_layernorm(const float* x, int M, int D, const float* g1, const float* b1, float eps1, void* out1,

@@ -433,6 +433,91 @@ def ffn_proj(x, ln0, w1, b1, act, slope, w2, b2, alpha, next_ln, wp, post_ln=Non
                        int(deff or x.shape[1]))
 
 
+_SRC_IMAGES = _ImageCache()
+
+
+def _build_src_image(ws, np_, stream):
+    (w,) = ws
+    n = int(lib().sbk_src_image_elems(w.shape[1]))
+    if n <= 0 or w.shape[0] != 256:
+        raise SbkError(f"sbk_src_image: unsupported shape {tuple(w.shape)}")
+    img = torch.empty(n, device=w.device, dtype=_bf16)
+    check(lib().sbk_src_image(ptr(w), w.shape[1], ptr(img), ctypes.c_void_p(stream.cuda_stream)), "sbk_src_image")
+    return img
+
+
+def src_image(ws):
+    """The weight-stream image of src_ffn_proj's source Linear (ws (256, Kin) bf16)."""
+    if ws.dtype != _bf16 or not ws.is_contiguous():
+        raise TypeError("src_image: contiguous bf16 weight")
+    return _SRC_IMAGES.get((ws,), 0, torch.cuda.current_stream(ws.device), build=_build_src_image)
+
+
+@custom_op("sbk::src_ffn_proj", mutates_args=())
+def _src_ffn_proj_op(a: torch.Tensor, ws: torch.Tensor, bs: Optional[torch.Tensor], rel_len: Optional[torch.Tensor],
+                     T: int, g0: torch.Tensor, b0: torch.Tensor, e0: float, w1: torch.Tensor, b1: torch.Tensor,
+                     act: int, slope: float, w2: torch.Tensor, b2: torch.Tensor, alpha: float,
+                     gp: Optional[torch.Tensor], bp: Optional[torch.Tensor], ep: float, gn: torch.Tensor,
+                     bn: torch.Tensor, en: float, wp: torch.Tensor,
+                     deff: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    M, D, NP = a.shape[0], ws.shape[0], wp.shape[0]
+    out = torch.empty(M, D, device=a.device, dtype=_f32)
+    y = torch.empty(M, NP, device=a.device, dtype=_bf16)
+    kpm = torch.empty(M // T, T, device=a.device, dtype=torch.uint8) if rel_len is not None else None
+    _src_ffn_proj_into(out, y, kpm, a, ws, bs, rel_len, T, g0, b0, e0, w1, b1, act, slope, w2, b2, alpha, gp, bp, ep,
+                       gn, bn, en, wp, deff)
+    return out, y, (kpm if kpm is not None else a.new_empty(0, dtype=torch.uint8))
+
+
+def _src_ffn_proj_into(out, y, kpm, a, ws, bs, rel_len, T, g0, b0, e0, w1, b1, act, slope, w2, b2, alpha, gp, bp, ep,
+                       gn, bn, en, wp, deff):
+    """The launch of sbk::src_ffn_proj into caller-owned out (>= M rows of D
+    fp32), y (>= M rows of NP bf16) and kpm (>= M bytes, or None)."""
+    M, Kin = a.shape
+    simg = src_image(ws)
+    img = ffn_image(w1, w2, wp=wp)
+    rc = lib().sbk_src_ffn_proj(ptr(a), Kin, ptr(simg), simg.numel(), ptr(bs), ptr(rel_len), int(T), ptr(kpm), M,
+                                ws.shape[0], deff, w1.shape[0], ptr(g0), ptr(b0), float(e0), ptr(img), img.numel(),
+                                ptr(b1), act, float(slope), ptr(b2), float(alpha), ptr(gp), ptr(bp), float(ep),
+                                ptr(out), ptr(gn), ptr(bn), float(en), wp.shape[0], ptr(y), stream_of(a))
+    check(rc, "sbk_src_ffn_proj")
+
+
+@_src_ffn_proj_op.register_fake
+def _(a, ws, bs, rel_len, T, g0, b0, e0, w1, b1, act, slope, w2, b2, alpha, gp, bp, ep, gn, bn, en, wp, deff):
+    return (a.new_empty((a.shape[0], ws.shape[0]), dtype=_f32), a.new_empty((a.shape[0], wp.shape[0]), dtype=_bf16),
+            a.new_empty((a.shape[0] // T, T) if rel_len is not None else (0,), dtype=torch.uint8))
+
+
+def src_ffn_proj_supported(D, Kin, H, NP):
+    """Shapes the fused src Linear + FFN + projection launch takes: whole
+    64-wide K-steps, and the 48 A rows of a workgroup fit in LDS (Kin <= 768)."""
+    return ffn_proj_supported(D, H, NP) and int(lib().sbk_src_image_elems(int(Kin))) > 0
+
+
+def src_ffn_proj(a, ws, bs, ln0, w1, b1, act, slope, w2, b2, alpha, next_ln, wp, post_ln=None, deff=None,
+                 rel_len=None, T=None):
+    """gemm(a, ws, bias=bs, fp32) followed by ffn_proj(.) in one launch: the
+    Linear's output rows stay on chip.  a (M, Kin), ws (256, Kin) bf16; bs
+    fp32 or None.  With rel_len (B floats) and T (M == B * T) the launch also
+    writes length_mask(rel_len, T).  Returns (out fp32, next_ln(out) · wp^T
+    bf16, mask (B, T) uint8 or None)."""
+    require_device(a, ws, w1, w2, wp)
+    if a.dtype != _bf16 or ws.dtype != _bf16 or not a.is_contiguous():
+        raise TypeError("src_ffn_proj: contiguous bf16 a and ws")
+    gp, bp, ep = post_ln if post_ln is not None else (None, None, 0.0)
+    if rel_len is not None:
+        require_device(rel_len)
+        if rel_len.dtype != _f32 or not rel_len.is_contiguous():
+            rel_len = rel_len.float().contiguous()
+        if T is None or a.shape[0] != rel_len.shape[0] * int(T):
+            raise ValueError(f"src_ffn_proj: {a.shape[0]} rows are not {rel_len.shape[0]} x T")
+    out, y, kpm = OPS.src_ffn_proj(a, ws, bs, rel_len, int(T or 1), ln0[0], ln0[1], float(ln0[2]), w1, b1, ACT[act],
+                                   float(slope), w2, b2, float(alpha), gp, bp, float(ep), next_ln[0], next_ln[1],
+                                   float(next_ln[2]), wp, int(deff or ws.shape[0]))
+    return out, y, (kpm if rel_len is not None else None)
+
+
 @custom_op("sbk::ffn_chain", mutates_args=())
 def _ffn_chain_op(x: torch.Tensor, act: int, slope: float, g0: torch.Tensor, b0: torch.Tensor, e0: float,
                   w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, alpha: float,
@@ -547,6 +632,63 @@ def conv_ffn_chain(x, B, T, pre, conv, kpm, a, b, act, slope, next_ln, wp, deff=
                               a[0][0], a[0][1], float(a[0][2]), a[1], a[2], a[3], a[4], float(a[5]), gp, bp, float(ep),
                               b[0][0], b[0][1], float(b[0][2]), b[1], b[2], b[3], b[4], float(b[5]), next_ln[0],
                               next_ln[1], float(next_ln[2]), wp, int(deff or x.shape[1]))
+
+
+@custom_op("sbk::conv_ffn_tail", mutates_args=())
+def _conv_ffn_tail_op(x: torch.Tensor, B: int, T: int, o: torch.Tensor, wo: torch.Tensor, bo: Optional[torch.Tensor],
+                      cg0: torch.Tensor, cb0: torch.Tensor, ce0: float, w1p: torch.Tensor, b1p: torch.Tensor,
+                      wc: torch.Tensor, bc: Optional[torch.Tensor], causal: bool, cg1: torch.Tensor,
+                      cb1: torch.Tensor, ce1: float, cw2: torch.Tensor, cb2: Optional[torch.Tensor],
+                      kpm: Optional[torch.Tensor], act: int, slope: float, g0: torch.Tensor, b0: torch.Tensor,
+                      e0: float, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, alpha: float,
+                      gp: Optional[torch.Tensor], bp: Optional[torch.Tensor], ep: float, gn: torch.Tensor,
+                      bn: torch.Tensor, en: float, deff: int) -> torch.Tensor:
+    if x.shape[0] != B * T:
+        raise ValueError(f"conv_ffn_tail: x has {x.shape[0]} rows, B * T = {B * T}")
+    u = torch.empty_like(x)
+    _conv_ffn_tail_into(u, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, causal, cg1, cb1, ce1, cw2, cb2, kpm,
+                        act, slope, g0, b0, e0, w1, b1, w2, b2, alpha, gp, bp, ep, gn, bn, en, deff)
+    return u
+
+
+def _conv_ffn_tail_into(u, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, causal, cg1, cb1, ce1, cw2, cb2, kpm,
+                        act, slope, g0, b0, e0, w1, b1, w2, b2, alpha, gp, bp, ep, gn, bn, en, deff):
+    """The launch of sbk::conv_ffn_tail into caller-owned u (>= B*T rows of D fp32)."""
+    cimg = conv_image(w1p, cw2)
+    img = ffn_image(w1, w2)
+    rc = lib().sbk_conv_ffn_tail(ptr(x), ptr(o), ptr(wo), ptr(bo), B, T, x.shape[1], deff, ptr(cg0), ptr(cb0),
+                                 float(ce0), ptr(cimg), cimg.numel(), ptr(b1p), ptr(wc), ptr(bc), wc.shape[0],
+                                 int(causal), ptr(cg1), ptr(cb1), float(ce1), ptr(cb2), ptr(kpm), w1.shape[0], act,
+                                 float(slope), ptr(g0), ptr(b0), float(e0), ptr(b1), ptr(b2), float(alpha), ptr(gp),
+                                 ptr(bp), float(ep), ptr(gn), ptr(bn), float(en), ptr(u), ptr(img), img.numel(),
+                                 stream_of(x))
+    check(rc, "sbk_conv_ffn_tail")
+
+
+@_conv_ffn_tail_op.register_fake
+def _(x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, causal, cg1, cb1, ce1, cw2, cb2, kpm, act, slope, g0, b0,
+      e0, w1, b1, w2, b2, alpha, gp, bp, ep, gn, bn, en, deff):
+    return torch.empty_like(x)
+
+
+def conv_ffn_tail_supported(D, K, H):
+    """Shapes the fused conv-module + last-FFN launch takes (as conv_ffn_chain's)."""
+    return conv_module_supported(D, K) and ffn_supported(D, H) and H <= 1024
+
+
+def conv_ffn_tail(x, B, T, pre, conv, kpm, a, final_ln, act="swish", slope=0.0, deff=None):
+    """conv_module(x, ..., pre=pre) followed by ffn(., a..., post_ln, next_ln=
+    final_ln, fp32) in one launch, the end of the encoder stack: only
+    final_ln(post_ln(z)) (B*T, D) fp32 is written.  pre, conv as
+    conv_ffn_chain's; a = (ln0, w1, b1, w2, b2, alpha, post_ln)."""
+    o, wo, bo = pre
+    cln0, w1p, b1p, wc, bc, causal, cln1, cw2, cb2 = conv
+    require_device(x, o, wo, w1p, cw2, a[1], a[3])
+    gp, bp, ep = a[6] if a[6] is not None else (None, None, 0.0)
+    return OPS.conv_ffn_tail(x, int(B), int(T), o, wo, bo, cln0[0], cln0[1], float(cln0[2]), w1p, b1p, wc, bc,
+                             bool(causal), cln1[0], cln1[1], float(cln1[2]), cw2, cb2, kpm, ACT[act], float(slope),
+                             a[0][0], a[0][1], float(a[0][2]), a[1], a[2], a[3], a[4], float(a[5]), gp, bp, float(ep),
+                             final_ln[0], final_ln[1], float(final_ln[2]), int(deff or x.shape[1]))
 
 
 def ffn(x, ln0, w1, b1, act, slope, w2, b2, alpha, post_ln=None, next_ln=None, next_dtype=_bf16, out=None, deff=None):

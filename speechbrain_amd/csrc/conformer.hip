@@ -963,7 +963,7 @@ __global__ void length_mask_kernel(const float* __restrict__ rel_len, int B, int
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * T) return;
   const int b = i / T, t = i - b * T;
-  out[i] = (float)t > floorf(rel_len[b] * (float)T) ? 1 : 0;
+  out[i] = length_mask_byte(rel_len[b], t, T);
 }
 
 // 4 values per thread (16-B loads, 8-B stores) when n % 4 == 0 and aligned

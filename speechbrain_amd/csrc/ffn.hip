@@ -72,6 +72,14 @@
 // one utterance; the module's output lands in the chain's residual layout
 // and never leaves the CU.  69.9 us per launch against 48.6 (chain) + 28.3
 // (conv module), 85.7 MB of HBM traffic against 110.2.
+// Round 8: the two ends of the stack.  conv_tail_kernel is the CONV prologue
+// in front of one block with post-LN and next-LN and no `out` (the last
+// layer: 47.0 us against 28.5 + 26.6).  src_ffn_kernel adds a second
+// prologue kind, SRC: the rows are A Ws^T + bs (the Linear in front of the
+// stack), its 48 A rows staged in the LDS that is free until LN0 writes Xn,
+// Ws streamed through the ring from its own image, the accumulators the
+// residual layout; it also stores its rows' key-padding bytes (37.6 us
+// against 32.9 + ~12 + 5.0).
 #include "mfma.h"
 
 using namespace sbk;
@@ -116,6 +124,15 @@ struct FfnArgs {
   // LN gains / biases and weight rows are zero there): inv_n = 1 / d_eff,
   // npad = D - d_eff (each padded zero adds mean^2 to the centred sum)
   float inv_n, npad;
+  // SRC: the rows come from a Linear in front of the block, x = sa . Ws^T + sbias
+  // (sa (M, Kin) bf16; simg: sbk_src_image(Ws), Kin / 64 tiles of Ws (256, Kin);
+  // sbias fp32 or null), and the workgroup stores the key-padding bytes of its
+  // rows, kpm_out[m] = length_mask_byte(rel_len[m / Tm], m % Tm, Tm) (rel_len null: none)
+  const bf16_t *sa, *simg;
+  const float* sbias;
+  int Kin, Tm;
+  const float* rel_len;
+  uint8_t* kpm_out;
 };
 
 __device__ __forceinline__ bf16x8 ld8(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
@@ -317,9 +334,11 @@ SBK_PROBE_BUFFER(g_ffn_tl, 16, 256)
 
 // The body of ffn_kernel and conv_chain_kernel.  CONV: the workgroup's rows
 // are one 48-frame tile of one utterance and come out of the convolution
-// module (conv_stage) in registers instead of from a.x.
-template <int D, int ACT, bool PROJ, bool CHAIN, bool CONV>
+// module (conv_stage) in registers instead of from a.x.  SRC: they come out of
+// the source Linear (a.sa . Ws^T + a.sbias) in registers.
+template <int D, int ACT, bool PROJ, bool CHAIN, bool CONV, bool SRC = false>
 __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* cs) {
+  static_assert(!(CONV && SRC), "one kind of prologue");
   constexpr int BM = FFN_BM, HC = 256, NW = FFN_NW, NT = FFN_NT;
   constexpr int XS = D + FFN_PAD, HS = HC + FFN_PAD;   // LDS row strides (elements), +32 B pad: conflict-free b128 reads
   constexpr int MT = BM / 16;                // m-tiles (3)
@@ -390,15 +409,17 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
   // tiles instead of being paid again after the last MFMA.
   constexpr int NRW = (BM + NW - 1) / NW;    // LN rows per wave
   f32x4 xres[T][MT];
-  if constexpr (CONV) {
+  if constexpr (CONV || SRC) {
     // ---- the convolution module in front of block A.  Its LDS ([0, CS_LDS))
     // lies under the ring, Xn and the hidden-chunk buffers; b1, the reduction
     // scratch and the parameter rows are past it and are staged while it
     // runs, and block A's LN0 affine waits in the tail of the second hidden
-    // buffer (free until chunk 1's activation step).
-    static_assert(T == 2 && MT == CS_MT3 && CHAIN && PROJ, "conv_stage hands over the chain's residual layout");
-    float* ga0 = reinterpret_cast<float*>(smem + CS_LDS);  // [g0 | b0] of block A
-    static_assert(CS_LDS + 2 * D * 4 <= (NB * TROWS * BK + BM * XS + 2 * BM * HS) * 2, "LN0 affine below b1");
+    // buffer (free until chunk 1's activation step).  SRC: the A rows of the
+    // source Linear lie over Xn and the hidden-chunk buffers, below the affine.
+    static_assert(T == 2 && MT == CS_MT3, "conv_stage hands over the chain's residual layout");
+    constexpr int HS_END = (NB * TROWS * BK + BM * XS + 2 * BM * HS) * 2;  // bytes
+    float* ga0 = reinterpret_cast<float*>(smem + (CONV ? CS_LDS : HS_END - 2 * D * 4));  // [g0 | b0] of block A
+    static_assert(CS_LDS + 2 * D * 4 <= HS_END, "LN0 affine below b1");
     static_assert(CS_LDS >= (NB * TROWS * BK + BM * XS + BM * HS) * 2, "LN0 affine in the second hidden buffer");
     const float* psrc = w == P_B2 ? a.b2 : w == P_GP ? a.gp : w == P_BP ? a.bp : w == P_G0B ? a.g0b
                       : w == P_B0B ? a.b0b : w == P_B2B ? a.b2b : w == P_GN ? a.gn : a.bn;
@@ -408,20 +429,109 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
     if (psrc) pv = *reinterpret_cast<const float4*>(psrc + lane * PER);
     if (b1t) {
       b1v = *reinterpret_cast<const float4*>(a.b1 + tid * 4);
-      b1bv = *reinterpret_cast<const float4*>(a.b1b + tid * 4);
+      if (CHAIN) b1bv = *reinterpret_cast<const float4*>(a.b1b + tid * 4);
     }
     if (tid < D / 2) gav = *reinterpret_cast<const float4*>((tid < D / 4 ? a.g0 : a.b0) + 4 * (tid % (D / 4)));
-    const int nblk = (cs->T + BM - 1) / BM, ub = blockIdx.x / nblk;
-    conv_stage(*cs, a.inv_n, a.npad, smem, ub, (blockIdx.x - ub * nblk) * BM, xres, [&]() __attribute__((always_inline)) {
+    auto stage_params = [&]() __attribute__((always_inline)) {
       if (psrc) *reinterpret_cast<float4*>(prm + w * D + lane * PER) = pv;
       if (b1t) {
         *reinterpret_cast<float4*>(b1s + tid * 4) = b1v;
-        *reinterpret_cast<float4*>(b1s + a.H + tid * 4) = b1bv;
+        if (CHAIN) *reinterpret_cast<float4*>(b1s + a.H + tid * 4) = b1bv;
       }
       if (tid < D / 2) *reinterpret_cast<float4*>(ga0 + 4 * tid) = gav;
-    });
-    // every wave is done with V and the conv ring: block A's first two tiles
-    // land under its LN0 (the conv module's output rows are A's residual)
+    };
+    if constexpr (CONV) {
+      const int nblk = (cs->T + BM - 1) / BM, ub = blockIdx.x / nblk;
+      conv_stage(*cs, a.inv_n, a.npad, smem, ub, (blockIdx.x - ub * nblk) * BM, xres, stage_params);
+    } else {
+      // ---- the source Linear: xres = A Ws^T + bs for the workgroup's 48 rows.
+      // The A rows (bf16, Kin <= 768) wait in LDS, row stride Kin + FFN_PAD (as
+      // Xn: conflict-free b128 fragment reads); Ws streams through the ring as
+      // Kin / 64 tiles of its 256 rows x 64 k (a.simg, the image's row
+      // swizzle), one tile in flight behind the one being read.  A step is a
+      // phase-1 step's wave map — wave w: output columns (2w + t) * 16 .. —
+      // so the accumulators are the residual layout.  Rows at or past M are
+      // copies of row M - 1 and are never stored.
+      bf16_t* As = Xn;
+      const int AS = a.Kin + FFN_PAD, KS = a.Kin / BK, cpr = a.Kin / 8;  // row stride, K-steps, 16-B chunks per row
+      // wave w: rows w + 8 i, lane: chunks lane and lane + 64 of a row (cpr <= 96)
+      constexpr int NRA = BM / NW;
+      static_assert(NRA * NW == BM && 768 / 8 <= 2 * 64, "two chunks per lane cover a row");
+      bf16x8 av[NRA * 2];
+#pragma unroll
+      for (int i = 0; i < NRA * 2; ++i) {
+        const int ch = min(lane + 64 * (i & 1), cpr - 1);
+        av[i] = ld8(a.sa + (long long)min(m0 + w + NW * (i >> 1), mlim - 1) * a.Kin + ch * 8);
+      }
+      f32x4 sb[T];
+#pragma unroll
+      for (int j = 0; j < T; ++j) {
+        sb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (a.sbias) sb[j] = *reinterpret_cast<const f32x4*>(a.sbias + (w * T + j) * 16 + 4 * g);
+      }
+      // the key-padding bytes of the workgroup's rows
+      if (a.rel_len && tid < BM && m0 + tid < mlim) {
+        const int m = m0 + tid, ub = m / a.Tm;
+        a.kpm_out[m] = length_mask_byte(a.rel_len[ub], m - ub * a.Tm, a.Tm);
+      }
+#pragma unroll
+      for (int i = 0; i < NRA * 2; ++i) {
+        const int ch = lane + 64 * (i & 1);
+        if (ch < cpr) *reinterpret_cast<bf16x8*>(As + (w + NW * (i >> 1)) * AS + ch * 8) = av[i];
+      }
+      stage_params();
+      __syncthreads();
+      auto issue_src = [&](int s, int slot) __attribute__((always_inline)) {
+        const bf16_t* src = a.simg + (long long)s * (TROWS * BK) + w * (GL * 512) + lane * 8;
+        bf16_t* dst = ring + slot * (TROWS * BK) + w * (GL * 512);
+        const auto gs = (const __attribute__((address_space(1))) void*)src;
+        const auto ls = (__attribute__((address_space(3))) void*)dst;
+        __builtin_amdgcn_global_load_lds(gs, ls, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(gs, ls, 16, 1024, 0);
+        __builtin_amdgcn_global_load_lds(gs, ls, 16, 2048, 0);
+        __builtin_amdgcn_global_load_lds(gs, ls, 16, 3072, 0);
+      };
+      issue_src(0, 0);
+      issue_src(min(1, KS - 1), 1);
+      f32x4 accs[T][MT];
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) accs[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int s = 0; s < KS; ++s) {
+        // this wave's rows of tile s landed (the tile behind it stays in flight)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL * (NB - 1)) : "memory");
+        const bf16_t* tile = ring + (s % NB) * TROWS * BK;
+        bf16x8 fw[BK / 32][T], fa[BK / 32][MT];
+#pragma unroll
+        for (int ks = 0; ks < BK / 32; ++ks) {
+#pragma unroll
+          for (int t = 0; t < T; ++t) {
+            const int row = w * (T * 16) + t * 16 + fr;
+            fw[ks][t] = ld8(tile + row * BK + (((ks * 4 + g) ^ ((row >> 1) & 7)) << 3));
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) fa[ks][mt] = ld8(As + (mt * 16 + fr) * AS + s * BK + ks * 32 + 8 * g);
+        }
+        // the slot takes tile s + 2 (at the end a harmless reload of the last tile)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_src(min(s + NB, KS - 1), s % NB);
+#pragma unroll
+        for (int ks = 0; ks < BK / 32; ++ks)
+#pragma unroll
+          for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) accs[t][mt] = FFN_MFMA(fw[ks][t], fa[ks][mt], accs[t][mt]);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail reloads before the ring is reused
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) xres[j][mt] = accs[j][mt] + sb[j];
+    }
+    // every wave is done with V and the conv ring (SRC: the A rows and the
+    // source tiles): block A's first two tiles land under its LN0 (the
+    // prologue's output rows are A's residual)
     lds_barrier();
     issue(0, 0);
     issue(1, 1);
@@ -827,8 +937,10 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
     return;
   }
   // all residual reads of x are done before out (which may alias x) is written
+  // (a null out is not stored: conv_tail_kernel keeps only u)
 #pragma unroll
   for (int j = 0; j < T; ++j) {
+    if (!a.out) break;
     const int d = (w * T + j) * 16 + 4 * g;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -875,6 +987,22 @@ __global__ void __launch_bounds__(FFN_NT) conv_chain_kernel(FfnArgs a, ConvStage
   ffn_body<256, ACT, true, true, true>(a, &c);
 }
 
+// [out_proj + residual + conv module] + [FFN2 + norm2 + the closing
+// LayerNorm] of the last layer on one 48-frame tile of one utterance: only
+// u = LNn(LNp(z)) goes to HBM.  Grid: B * ceil(T / 48).
+template <int ACT>
+__global__ void __launch_bounds__(FFN_NT) conv_tail_kernel(FfnArgs a, ConvStageArgs c) {
+  ffn_body<256, ACT, false, false, true>(a, &c);
+}
+
+// [src Linear (+ key-padding bytes)] + [FFN1 + norm1 + in_proj of layer 0]:
+// ffn_kernel<256, ACT, true, false> on rows that come out of a.sa . Ws^T + bs
+// in registers.  Grid: ceil(M / 48), the flat row tiling of ffn_kernel.
+template <int ACT>
+__global__ void __launch_bounds__(FFN_NT) src_ffn_kernel(FfnArgs a) {
+  ffn_body<256, ACT, true, false, false, true>(a, nullptr);
+}
+
 template <int D>
 size_t ffn_lds(int H, bool chain) {
   // 2-slot weight ring, Xn, two hidden-chunk buffers, b1 (two with CHAIN), the row-reduction scratch,
@@ -913,23 +1041,47 @@ int ffn_dispatch(const FfnArgs& a, hipStream_t s) {
 }
 
 template <int ACT>
-int launch_conv_chain_act(const FfnArgs& a, const ConvStageArgs& c, unsigned grid, size_t lds, hipStream_t s) {
-  if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&conv_chain_kernel<ACT>), lds)) return (int)e;
-  hipLaunchKernelGGL((conv_chain_kernel<ACT>), dim3(grid), dim3(FFN_NT), lds, s, a, c);
+int launch_src_ffn_act(const FfnArgs& a, size_t lds, hipStream_t s) {
+  if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&src_ffn_kernel<ACT>), lds)) return (int)e;
+  hipLaunchKernelGGL((src_ffn_kernel<ACT>), dim3((a.M + FFN_BM - 1) / FFN_BM), dim3(FFN_NT), lds, s, a);
   return 0;
 }
 
+int src_ffn_dispatch(const FfnArgs& a, hipStream_t s) {
+  const size_t lds = ffn_lds<256>(a.H, false);
+  // the A rows, row stride Kin + FFN_PAD, lie over Xn and the hidden-chunk buffers below the LN0 affine
+  if (lds > 160 * 1024 || (size_t)FFN_BM * (a.Kin + FFN_PAD) > (size_t)3 * FFN_BM * (256 + FFN_PAD) - 2 * 256 * 2)
+    return SBK_ERR_ARG;
+  switch (a.act) {
+    case ACT_SWISH: return launch_src_ffn_act<ACT_SWISH>(a, lds, s);
+    case ACT_LRELU: return launch_src_ffn_act<ACT_LRELU>(a, lds, s);
+    case ACT_GELU: return launch_src_ffn_act<ACT_GELU>(a, lds, s);
+    case ACT_NONE: return launch_src_ffn_act<ACT_NONE>(a, lds, s);
+    default: return SBK_ERR_ARG;
+  }
+}
+
+template <int ACT, bool TAIL>
+int launch_conv_chain_act(const FfnArgs& a, const ConvStageArgs& c, unsigned grid, size_t lds, hipStream_t s) {
+  const auto kern = TAIL ? &conv_tail_kernel<ACT> : &conv_chain_kernel<ACT>;
+  if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(kern), lds)) return (int)e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(FFN_NT), lds, s, a, c);
+  return 0;
+}
+
+// TAIL: one block and no projection (conv_tail_kernel)
+template <bool TAIL>
 int conv_chain_dispatch(const FfnArgs& a, const ConvStageArgs& c, hipStream_t s) {
-  const size_t lds = ffn_lds<256>(a.H, true);
+  const size_t lds = ffn_lds<256>(a.H, !TAIL);
   static_assert(CS_LDS + 2 * 256 * 4 <= (2 * 256 * 64 + FFN_BM * (256 + FFN_PAD) * 3) * 2, "the conv stage lies under ring, Xn, Hs");
   if (lds > 160 * 1024) return SBK_ERR_ARG;
   const long long grid = (long long)c.B * ((c.T + FFN_BM - 1) / FFN_BM);
   if (grid > 0x7fffffffLL) return SBK_ERR_ARG;
   switch (a.act) {
-    case ACT_SWISH: return launch_conv_chain_act<ACT_SWISH>(a, c, (unsigned)grid, lds, s);
-    case ACT_LRELU: return launch_conv_chain_act<ACT_LRELU>(a, c, (unsigned)grid, lds, s);
-    case ACT_GELU: return launch_conv_chain_act<ACT_GELU>(a, c, (unsigned)grid, lds, s);
-    case ACT_NONE: return launch_conv_chain_act<ACT_NONE>(a, c, (unsigned)grid, lds, s);
+    case ACT_SWISH: return launch_conv_chain_act<ACT_SWISH, TAIL>(a, c, (unsigned)grid, lds, s);
+    case ACT_LRELU: return launch_conv_chain_act<ACT_LRELU, TAIL>(a, c, (unsigned)grid, lds, s);
+    case ACT_GELU: return launch_conv_chain_act<ACT_GELU, TAIL>(a, c, (unsigned)grid, lds, s);
+    case ACT_NONE: return launch_conv_chain_act<ACT_NONE, TAIL>(a, c, (unsigned)grid, lds, s);
     default: return SBK_ERR_ARG;
   }
 }
@@ -1033,8 +1185,9 @@ SBK_API int sbk_ffn_image(const void* w1, const void* w2, const void* w1b, const
 namespace {
 int ffn_check(const float* x, int M, int D, int H, const float* g0, const float* b0, const void* img,
               long long img_elems, int chain, const float* b1, int act, const float* b2, const float* gp,
-              const float* bp, float* out, const float* gn, const float* bn, void* u, int np, void* yp) {
-  if (M <= 0 || !sbk_ffn_supported(D, H) || !g0 || !b0 || !img || !b1 || !b2 || !out) return SBK_ERR_ARG;
+              const float* bp, float* out, const float* gn, const float* bn, void* u, int np, void* yp,
+              bool out_opt = false) {
+  if (M <= 0 || !sbk_ffn_supported(D, H) || !g0 || !b0 || !img || !b1 || !b2 || (!out && !out_opt)) return SBK_ERR_ARG;
   // the image must be the one sbk_ffn_image built for this (D, H, np, chain):
   // the kernel streams exactly that many tiles from it
   if (np < 0 || np % 256 || img_elems != sbk_ffn_image_elems(D, H, np, chain)) return SBK_ERR_ARG;
@@ -1060,7 +1213,7 @@ SBK_API int sbk_ffn_proj(const float* x, int M, int D, int d_eff, int H, const f
   if (ffn_check(x, M, D, H, g0, b0, img, img_elems, 0, b1, act, b2, gp, bp, out, gn, bn, u, np, yp) || d_eff <= 0 ||
       d_eff > D)
     return SBK_ERR_ARG;
-  FfnArgs a;
+  FfnArgs a{};
   a.inv_n = 1.0f / (float)d_eff; a.npad = (float)(D - d_eff);
   a.x = x; a.M = M; a.H = H;
   a.g0 = g0; a.b0 = b0; a.eps0 = eps0;
@@ -1096,7 +1249,7 @@ SBK_API int sbk_ffn_chain(const float* x, int M, int D, int d_eff, int H, int ac
   if (ffn_check(x, M, D, H, g0, b0, img, img_elems, 1, b1, act, b2, gp, bp, out, gn, bn, u, np, yp) || d_eff <= 0 ||
       d_eff > D)
     return SBK_ERR_ARG;
-  FfnArgs a;
+  FfnArgs a{};
   a.inv_n = 1.0f / (float)d_eff; a.npad = (float)(D - d_eff);
   a.x = x; a.M = M; a.H = H;
   a.g0 = g0; a.b0 = b0; a.eps0 = eps0;
@@ -1122,6 +1275,67 @@ SBK_API int sbk_ffn(const float* x, int M, int D, int d_eff, int H, const float*
                       epsn, u, u_bf16, 0, nullptr, stream);
 }
 
+// The source Linear's weight ws (256, Kin) bf16 as Kin / 64 tiles of 256 rows
+// x 64 k in K order, rows swizzled as in sbk_ffn_image: the weight stream of
+// sbk_src_ffn_proj's first stage.  Kin % 64 == 0, Kin <= 768 (the 48 A rows
+// of a workgroup wait in LDS).
+SBK_API long long sbk_src_image_elems(int Kin) {
+  return Kin > 0 && Kin % 64 == 0 && Kin <= 768 ? (long long)(Kin / 64) * 256 * 64 : -1;
+}
+
+SBK_API int sbk_src_image(const void* ws, int Kin, void* img, void* stream) {
+  if (sbk_src_image_elems(Kin) < 0 || !ws || !img) return SBK_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(img)) & 15) return SBK_ERR_ARG;
+  // one "projection" of 256 columns over K = Kin: tile s = rows 0 .. 255, k s*64 ..
+  ImgSrc q{};
+  q.wp = reinterpret_cast<const bf16_t*>(ws);
+  q.D = Kin; q.H = 0; q.chain = 0; q.ntile_blk = 0; q.ntile_ffn = 0;
+  const int nt = Kin / 64;
+  hipLaunchKernelGGL(ffn_image_kernel, dim3(nt * 8), dim3(256), 0, (hipStream_t)stream, q, nt,
+                     reinterpret_cast<bf16_t*>(img));
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
+// sbk_gemm (the src Linear: x = a ws^T + sbias, a (M, Kin) bf16, simg =
+// sbk_src_image(ws)) followed by sbk_ffn_proj on x in one launch: x never
+// reaches HBM.  With rel_len (B floats, M == B * T) the launch also writes the
+// key-padding mask kpm_out (M bytes) as sbk_length_mask does; rel_len null:
+// no mask (kpm_out unused).  out (M, D) fp32, yp (M, np) bf16, np > 0.
+SBK_API int sbk_src_ffn_proj(const void* a_, int Kin, const void* simg, long long simg_elems, const float* sbias,
+                             const float* rel_len, int T, unsigned char* kpm_out, int M, int D, int d_eff, int H,
+                             const float* g0, const float* b0, float eps0, const void* img, long long img_elems,
+                             const float* b1, int act, float slope, const float* b2, float alpha, const float* gp,
+                             const float* bp, float epsp, float* out, const float* gn, const float* bn, float epsn,
+                             int np, void* yp, void* stream) {
+  if (!a_ || !simg || sbk_src_image_elems(Kin) < 0 || simg_elems != sbk_src_image_elems(Kin) || np <= 0) return SBK_ERR_ARG;
+  if (rel_len && (!kpm_out || T <= 0 || M % T)) return SBK_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(a_) | reinterpret_cast<uintptr_t>(simg) | reinterpret_cast<uintptr_t>(sbias)) & 15)
+    return SBK_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(rel_len) & 3) return SBK_ERR_ARG;
+  // ffn_check's x: the rows are not read from memory; `out` stands in (checked as out)
+  if (ffn_check(out, M, D, H, g0, b0, img, img_elems, 0, b1, act, b2, gp, bp, out, gn, bn, nullptr, np, yp) ||
+      d_eff <= 0 || d_eff > D)
+    return SBK_ERR_ARG;
+  if (reinterpret_cast<const void*>(out) == a_) return SBK_ERR_ARG;
+  FfnArgs a{};
+  a.inv_n = 1.0f / (float)d_eff; a.npad = (float)(D - d_eff);
+  a.x = nullptr; a.M = M; a.H = H;
+  a.g0 = g0; a.b0 = b0; a.eps0 = eps0;
+  a.img = reinterpret_cast<const bf16_t*>(img); a.b1 = b1; a.act = act; a.slope = slope;
+  a.b2 = b2; a.alpha = alpha;
+  a.gp = gp; a.bp = bp; a.epsp = epsp;
+  a.out = out;
+  a.gn = gn; a.bn = bn; a.epsn = epsn; a.u = nullptr; a.u_bf16 = 1;
+  a.np = np; a.yp = reinterpret_cast<bf16_t*>(yp);
+  a.sa = reinterpret_cast<const bf16_t*>(a_); a.simg = reinterpret_cast<const bf16_t*>(simg); a.sbias = sbias;
+  a.Kin = Kin; a.Tm = T; a.rel_len = rel_len; a.kpm_out = rel_len ? kpm_out : nullptr;
+  const int rc = src_ffn_dispatch(a, (hipStream_t)stream);
+  if (rc) return rc;
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
 SBK_API long long sbk_conv_image_elems(int D) { return D == CS_D ? (long long)(CS_P1T + CS_P3T) * CS_TILE : -1; }
 
 SBK_API int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, void* stream) {
@@ -1134,6 +1348,33 @@ SBK_API int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, vo
   SBK_CHECK_LAUNCH();
   return 0;
 }
+
+namespace {
+// the convolution-module stage's arguments of sbk_conv_ffn_chain / sbk_conv_ffn_tail, checked
+int conv_stage_args(ConvStageArgs& c, const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D,
+                    int d_eff, const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg,
+                    long long cimg_elems, const float* cb1p, const float* wc, const float* bc, int K, int causal,
+                    const float* cln1_w, const float* cln1_b, float ceps1, const float* cb2, const unsigned char* kpm,
+                    const void* out) {
+  if (B <= 0 || T <= 0 || (long long)B * T > 0x7fffffffLL || D != CS_D || K < 1 || K > CS_KMAX || !x || !out ||
+      x == out || d_eff <= 0 || d_eff > D)
+    return SBK_ERR_ARG;
+  if (!o || !wo || !cln0_w || !cln0_b || !cimg || !cb1p || !wc || !cln1_w || !cln1_b) return SBK_ERR_ARG;
+  if (cimg_elems != sbk_conv_image_elems(D)) return SBK_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(wo) | reinterpret_cast<uintptr_t>(bo) |
+       reinterpret_cast<uintptr_t>(cln0_w) | reinterpret_cast<uintptr_t>(cln0_b) | reinterpret_cast<uintptr_t>(cimg) |
+       reinterpret_cast<uintptr_t>(cb1p) | reinterpret_cast<uintptr_t>(cln1_w) | reinterpret_cast<uintptr_t>(cln1_b) |
+       reinterpret_cast<uintptr_t>(cb2)) & 15)
+    return SBK_ERR_ARG;
+  c.x = x; c.B = B; c.T = T; c.K = K; c.padL = causal ? K - 1 : (K - 1) / 2;
+  c.g0 = cln0_w; c.b0 = cln0_b; c.eps0 = ceps0;
+  c.img = reinterpret_cast<const bf16_t*>(cimg); c.b1 = cb1p; c.wc = wc; c.bc = bc;
+  c.g1 = cln1_w; c.b1n = cln1_b; c.eps1 = ceps1;
+  c.b2 = cb2; c.kpm = reinterpret_cast<const uint8_t*>(kpm);
+  c.o = reinterpret_cast<const bf16_t*>(o); c.wo = reinterpret_cast<const bf16_t*>(wo); c.bo = bo;
+  return 0;
+}
+}  // namespace
 
 // sbk_conv_module_pre followed by sbk_ffn_chain (with the projection tail) in
 // one launch: x_c = x + o wo^T + bo through the convolution module (c*
@@ -1150,22 +1391,18 @@ SBK_API int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, co
                                const float* b1b, const float* b2b, float alphab, float* out, const float* gn,
                                const float* bn, float epsn, const void* img, long long img_elems, int np, void* yp,
                                void* stream) {
-  if (B <= 0 || T <= 0 || (long long)B * T > 0x7fffffffLL || D != CS_D || K < 1 || K > CS_KMAX || !x || !out ||
-      x == out || d_eff <= 0 || d_eff > D)
+  ConvStageArgs c;
+  if (conv_stage_args(c, x, o, wo, bo, B, T, D, d_eff, cln0_w, cln0_b, ceps0, cimg, cimg_elems, cb1p, wc, bc, K, causal,
+                      cln1_w, cln1_b, ceps1, cb2, kpm, out))
     return SBK_ERR_ARG;
-  if (!o || !wo || !cln0_w || !cln0_b || !cimg || !cb1p || !wc || !cln1_w || !cln1_b) return SBK_ERR_ARG;
-  if (cimg_elems != sbk_conv_image_elems(D)) return SBK_ERR_ARG;
   if (!g0b || !b0b || !b1b || !b2b || !gn || !bn || !yp || np <= 0) return SBK_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(wo) | reinterpret_cast<uintptr_t>(bo) |
-       reinterpret_cast<uintptr_t>(cln0_w) | reinterpret_cast<uintptr_t>(cln0_b) | reinterpret_cast<uintptr_t>(cimg) |
-       reinterpret_cast<uintptr_t>(cb1p) | reinterpret_cast<uintptr_t>(cln1_w) | reinterpret_cast<uintptr_t>(cln1_b) |
-       reinterpret_cast<uintptr_t>(cb2) | reinterpret_cast<uintptr_t>(g0b) | reinterpret_cast<uintptr_t>(b0b) |
-       reinterpret_cast<uintptr_t>(b1b) | reinterpret_cast<uintptr_t>(b2b)) & 15)
+  if ((reinterpret_cast<uintptr_t>(g0b) | reinterpret_cast<uintptr_t>(b0b) | reinterpret_cast<uintptr_t>(b1b) |
+       reinterpret_cast<uintptr_t>(b2b)) & 15)
     return SBK_ERR_ARG;
   const int M = B * T;
   if (ffn_check(x, M, D, H, g0, b0, img, img_elems, 1, b1, act, b2, gp, bp, out, gn, bn, nullptr, np, yp))
     return SBK_ERR_ARG;
-  FfnArgs a;
+  FfnArgs a{};
   a.inv_n = 1.0f / (float)d_eff; a.npad = (float)(D - d_eff);
   a.x = x; a.M = M; a.H = H;
   a.g0 = g0; a.b0 = b0; a.eps0 = eps0;
@@ -1177,14 +1414,45 @@ SBK_API int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, co
   a.np = np; a.yp = reinterpret_cast<bf16_t*>(yp);
   a.g0b = g0b; a.b0b = b0b; a.eps0b = eps0b;
   a.b1b = b1b; a.b2b = b2b; a.alphab = alphab;
+  const int rc = conv_chain_dispatch<false>(a, c, (hipStream_t)stream);
+  if (rc) return rc;
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
+// sbk_conv_module_pre followed by sbk_ffn with its post-LN and next-LN in one
+// launch, the end of the encoder stack: the last layer's convolution module,
+// FFN2 + norm2 (g0 .. epsp) and the closing LayerNorm (gn, bn).  Only
+// u (B*T, D) fp32 = LNn(LNp(x_c + alpha FFN(LN0(x_c)))) is written; it must
+// not alias x.  img = sbk_ffn_image(w1, w2) of one block, no projection.
+SBK_API int sbk_conv_ffn_tail(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D,
+                              int d_eff, const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg,
+                              long long cimg_elems, const float* cb1p, const float* wc, const float* bc, int K,
+                              int causal, const float* cln1_w, const float* cln1_b, float ceps1, const float* cb2,
+                              const unsigned char* kpm, int H, int act, float slope, const float* g0, const float* b0,
+                              float eps0, const float* b1, const float* b2, float alpha, const float* gp,
+                              const float* bp, float epsp, const float* gn, const float* bn, float epsn, float* u,
+                              const void* img, long long img_elems, void* stream) {
   ConvStageArgs c;
-  c.x = x; c.B = B; c.T = T; c.K = K; c.padL = causal ? K - 1 : (K - 1) / 2;
-  c.g0 = cln0_w; c.b0 = cln0_b; c.eps0 = ceps0;
-  c.img = reinterpret_cast<const bf16_t*>(cimg); c.b1 = cb1p; c.wc = wc; c.bc = bc;
-  c.g1 = cln1_w; c.b1n = cln1_b; c.eps1 = ceps1;
-  c.b2 = cb2; c.kpm = reinterpret_cast<const uint8_t*>(kpm);
-  c.o = reinterpret_cast<const bf16_t*>(o); c.wo = reinterpret_cast<const bf16_t*>(wo); c.bo = bo;
-  const int rc = conv_chain_dispatch(a, c, (hipStream_t)stream);
+  if (conv_stage_args(c, x, o, wo, bo, B, T, D, d_eff, cln0_w, cln0_b, ceps0, cimg, cimg_elems, cb1p, wc, bc, K, causal,
+                      cln1_w, cln1_b, ceps1, cb2, kpm, u))
+    return SBK_ERR_ARG;
+  if (!gn || !bn) return SBK_ERR_ARG;
+  const int M = B * T;
+  if (ffn_check(x, M, D, H, g0, b0, img, img_elems, 0, b1, act, b2, gp, bp, nullptr, gn, bn, u, 0, nullptr, true))
+    return SBK_ERR_ARG;
+  FfnArgs a{};
+  a.inv_n = 1.0f / (float)d_eff; a.npad = (float)(D - d_eff);
+  a.x = x; a.M = M; a.H = H;
+  a.g0 = g0; a.b0 = b0; a.eps0 = eps0;
+  a.img = reinterpret_cast<const bf16_t*>(img); a.b1 = b1; a.act = act; a.slope = slope;
+  a.b2 = b2; a.alpha = alpha;
+  a.gp = gp; a.bp = bp; a.epsp = epsp;
+  a.out = nullptr;
+  a.gn = gn; a.bn = bn; a.epsn = epsn; a.u = u; a.u_bf16 = 0;
+  a.np = 0; a.yp = nullptr;
+  a.g0b = nullptr; a.b0b = nullptr; a.eps0b = 0.f; a.b1b = nullptr; a.b2b = nullptr; a.alphab = 0.f;
+  const int rc = conv_chain_dispatch<true>(a, c, (hipStream_t)stream);
   if (rc) return rc;
   SBK_CHECK_LAUNCH();
   return 0;

@@ -138,6 +138,13 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// key-padding byte of frame t of an utterance of relative length rel_len over
+// T frames (TransformerASR.py:295-301: arange(T) > floor(wav_len * T)); the one
+// expression behind length_mask_kernel and the mask stores of src_ffn_kernel
+__device__ __forceinline__ uint8_t length_mask_byte(float rel_len, int t, int T) {
+  return (float)t > floorf(rel_len * (float)T) ? 1 : 0;
+}
+
 // Block-wide sum for blockDim.x a multiple of 64 (<= 1024). `red` >= 16 floats.
 // Block-wide max (all threads get the result); red: >= blockDim/64 floats.
 __device__ __forceinline__ float block_max(float v, float* red) {

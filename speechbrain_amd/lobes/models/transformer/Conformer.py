@@ -48,6 +48,12 @@ USE_LAYER_CHAIN = True
 # (sbk_conv_ffn_chain): its output rows stay on the CU as the chain's input,
 # two launches per layer instead of three
 USE_CONV_CHAIN = True
+# the end of the stack in one launch (sbk_conv_ffn_tail): the last layer's
+# conv module in front of its FFN2 + norm2 + the closing LayerNorm
+USE_FUSED_ENDS = True
+# the linear_pos projection of the relative table kept across inference calls
+# (ConformerEncoder.projected_pos) instead of one GEMM per call
+USE_POS_CACHE = True
 # bf16 stacks with d_model < 256 (conformer_small.yaml: 144) on a zero-padded
 # D = 256 copy, so they take the fused kernels (_PaddedEncoder)
 USE_PADDED_SHADOW = True
@@ -361,6 +367,8 @@ class ConformerEncoder(nn.Module):
         self.norm = LayerNorm(d_model, eps=1e-6)
         self.attention_type = attention_type
         self._wc = _enc.WeightCache()
+        self._pk = {}        # (device, dtype) -> (signature, Tc, projected table): projected_pos
+        self._pk_keep = []
 
     def stacked_pos_weight(self, dtype):
         """linear_pos weights of all layers stacked (L*d, d) in the compute dtype,
@@ -392,19 +400,74 @@ class ConformerEncoder(nn.Module):
             return _PaddedEncoder.of(self)
         return None
 
-    def run(self, src2d, B, T, pos_embs, kpm_u8, dtype, need_attn, am=None):
+    def projected_pos(self, pos, T, dtype, pos_key=None):
+        """p_k of every layer, (2T-1, L*d): pos · stacked linear_pos^T.
+
+        pos_key (hashable, or None): the caller's word that pos is the
+        length-T member of one family of relative tables — row r of the table
+        for T is row r + (Tc - T) of the table for any Tc >= T
+        (RelPosEncXL.table) — named by the key.  The GEMM is row-wise and its
+        inputs are constants of an inference run, so the projection of the
+        longest table seen so far is kept per (device, dtype) and a call at
+        T <= Tc is served the centred row slice [Tc - T, Tc + T - 1) of it, a
+        view (the attention kernels take pk.stride(0)).  A longer T or a
+        changed linear_pos weight (storage or version) replaces the entry.
+        Under torch.jit.trace the GEMM stays (the trace keeps its node); a
+        capturing stream reads the entry but never fills it (a tensor
+        allocated in a capture belongs to that graph's pool)."""
+        W = self.stacked_pos_weight(dtype)
+        if not USE_POS_CACHE or pos_key is None or torch.jit.is_tracing():
+            return _enc.gemm(pos, W, out_dtype=dtype)
+        key = (str(pos.device), dtype)
+        ws = [layer.mha_layer.linear_pos.weight for layer in self.layers]
+        sig = (pos_key, pos.shape[1]) + tuple((p.data_ptr(), p._version, p.device) for p in ws)
+        hit = self._pk.get(key)
+        if hit is not None and hit[0] == sig and hit[1] >= T:
+            Tc = hit[1]
+            if torch.cuda.is_current_stream_capturing() and not any(t is hit[2] for t in self._pk_keep):
+                self._pk_keep.append(hit[2])  # a captured graph reads it: it outlives a replacement
+            return hit[2][Tc - T:Tc + T - 1]
+        pk = _enc.gemm(pos, W, out_dtype=dtype)
+        if not torch.cuda.is_current_stream_capturing():
+            self._pk[key] = (sig, T, pk)
+        return pk
+
+    def takes_src(self, Kin, dtype):
+        """True when run(src=...) applies: the chained bf16 stack at D = 256
+        whose first launch can run the Linear in front of it
+        (sbk_src_ffn_proj: Kin in whole 64-wide K-steps that fit in LDS)."""
+        if not (USE_FUSED_ENDS and USE_LAYER_CHAIN and dtype == _bf16):
+            return False
+        l0 = self.layers[0]
+        d = self.norm.norm.weight.shape[0]
+        if d != PAD_D or not (all(layer.chainable(dtype, d) for layer in self.layers) and self._uniform_ffns()):
+            return False
+        return _enc.src_ffn_proj_supported(d, Kin, l0.ffn_module1[1].ffn[0].out_features,
+                                           l0.mha_layer.fused_in_proj(dtype).shape[0])
+
+    def run(self, src2d, B, T, pos_embs, kpm_u8, dtype, need_attn, am=None, pos_key=None, src=None):
         """Fused stack on (B*T, d) fp32 → ((B*T, d) fp32, [attn]); am: the
         src_mask as _enc.attn_mask_arg (takes the per-layer path).  A bf16
         stack with d_model < 256 runs on its zero-padded D = 256 shadow
-        (_PaddedEncoder) when that shadow takes the layer chain."""
+        (_PaddedEncoder) when that shadow takes the layer chain.  pos_key: see
+        projected_pos.  src = (a (B*T, Kin) bf16, ws (256, Kin) bf16, bs,
+        rel_len or None) in place of src2d, where takes_src() holds: the rows
+        are a · ws^T + bs, computed by the first launch, which also writes the
+        key padding mask from rel_len when kpm_u8 is None."""
+        if src is not None:
+            # the caller asked takes_src(): the chained stack, its first launch on a · ws^T + bs
+            d = src[1].shape[0]
+            pos = _enc.to_compute(pos_embs.reshape(-1, d), dtype)
+            return self._run_chain(None, B, T, pos, kpm_u8, dtype, need_attn, self.projected_pos(pos, T, dtype, pos_key),
+                                   src=src)
         if self.wants_train_path(src2d):
             return self.train_run(src2d, B, T, pos_embs, kpm_u8, dtype, am=am)
         d = src2d.shape[1]
         sh = self._shadow(d, dtype, am)
         if sh is not None:
-            return sh.run(src2d, B, T, pos_embs, kpm_u8, dtype, need_attn)
+            return sh.run(src2d, B, T, pos_embs, kpm_u8, dtype, need_attn, pos_key=pos_key)
         pos = _enc.to_compute(pos_embs.reshape(-1, d), dtype)
-        pk_all = _enc.gemm(pos, self.stacked_pos_weight(dtype), out_dtype=dtype)  # (2T-1, L*d)
+        pk_all = self.projected_pos(pos, T, dtype, pos_key)  # (2T-1, L*d)
         x = src2d
         u = None
         attns = []
@@ -432,19 +495,32 @@ class ConformerEncoder(nn.Module):
         f = [m[1] for layer in self.layers for m in (layer.ffn_module1, layer.ffn_module2)]
         return all(x.act_name() == f[0].act_name() and x.ffn[0].out_features == f[0].ffn[0].out_features for x in f)
 
-    def _run_chain(self, x, B, T, pos, kpm_u8, dtype, need_attn, pk_all):
+    def _run_chain(self, x, B, T, pos, kpm_u8, dtype, need_attn, pk_all, src=None):
         """The fused stack as 3 launches per layer: [FFN2_i + norm2_i +
         FFN1_{i+1} + norm1_{i+1} + in_proj_{i+1}] (sbk_ffn_chain), attention,
         [out_proj + residual + conv module] (sbk_conv_module_pre); layer 0's
         FFN1 is sbk_ffn_proj, the last FFN2 carries the closing LayerNorm.
         With USE_CONV_CHAIN the conv module of layers 0 .. n-2 runs in front
-        of the chain in the same launch (sbk_conv_ffn_chain): 2 per layer."""
-        d = x.shape[1]
+        of the chain in the same launch (sbk_conv_ffn_chain): 2 per layer.
+        With USE_FUSED_ENDS the last layer's conv module runs in front of
+        its FFN2 + norm2 + the closing LayerNorm (sbk_conv_ffn_tail), and
+        with src = (a, ws, bs, rel_len) in place of x the Linear in front of
+        the stack and the key padding mask run in layer 0's launch
+        (sbk_src_ffn_proj)."""
         ln = ConformerEncoderLayer._ln
         L = self.layers
         l0 = L[0]
         f1 = l0.ffn_module1
-        x, qkv = f1[1].run_fused_proj(x, ln(l0, f1[0]), 0.5, ln(l0, l0.norm1.norm), l0.mha_layer.fused_in_proj(dtype))
+        if src is not None:
+            # the Linear in front of the stack (and the key padding mask, unless the caller brought one) in layer 0's launch
+            a_, ws, bs, rel_len = src
+            x, qkv, kpm = f1[1].run_fused_src_proj(a_, ws, bs, ln(l0, f1[0]), 0.5, ln(l0, l0.norm1.norm),
+                                                   l0.mha_layer.fused_in_proj(dtype),
+                                                   rel_len=rel_len if kpm_u8 is None else None, T=T)
+            kpm_u8 = kpm if kpm is not None else kpm_u8
+        else:
+            x, qkv = f1[1].run_fused_proj(x, ln(l0, f1[0]), 0.5, ln(l0, l0.norm1.norm), l0.mha_layer.fused_in_proj(dtype))
+        d = x.shape[1]
         attns = []
         for i, layer in enumerate(L):
             _, attn, pre = layer.mha_layer.attend_heads(None, B, T, pos, kpm_u8, dtype, need_attn,
@@ -466,10 +542,17 @@ class ConformerEncoder(nn.Module):
                 x = cm.run_fused(x, B, T, kpm_u8, pre=pre)
                 x, qkv = _enc.ffn_chain(x, a, b, act, slope, ln(nl, nl.norm1.norm), wp, deff=f2[1]._deff)
             else:
-                x = cm.run_fused(x, B, T, kpm_u8, pre=pre)
                 fn = self.norm.norm
+                final_ln = (fn.weight.detach(), fn.bias.detach(), fn.eps)
+                a = f2[1].chain_block(ln(layer, f2[0]), 0.5, post_ln=ln(layer, layer.norm2.norm))
+                if USE_FUSED_ENDS and _enc.conv_ffn_tail_supported(d, cm.conv.weight.shape[-1], a[1].shape[0]):
+                    act, slope = f2[1].act_name()
+                    y = _enc.conv_ffn_tail(x, B, T, pre, cm.fused_params(), kpm_u8, a, final_ln, act, slope,
+                                           deff=f2[1]._deff)
+                    return y, attns
+                x = cm.run_fused(x, B, T, kpm_u8, pre=pre)
                 _, y = f2[1].run_fused(x, ln(layer, f2[0]), 0.5, post_ln=ln(layer, layer.norm2.norm),
-                                       next_ln=(fn.weight.detach(), fn.bias.detach(), fn.eps), next_dtype=_f32)
+                                       next_ln=final_ln, next_dtype=_f32)
                 return y, attns
 
     def forward(self, src, src_mask: Optional[torch.Tensor] = None,
@@ -628,12 +711,15 @@ class _PaddedEncoder:
             self._pos = {key: pos}
         return pos
 
-    def run(self, src2d, B, T, pos_embs, kpm_u8, dtype, need_attn):
+    def run(self, src2d, B, T, pos_embs, kpm_u8, dtype, need_attn, pos_key=None, src=None):
         d = self.d
-        if src2d.shape[1] == PAD_D:  # already padded by the producer (TransformerASR's padded src Linear)
+        if src is not None:  # (a, zero-row-padded ws, bs, rel_len): see ConformerEncoder.run
+            x = None
+        elif src2d.shape[1] == PAD_D:  # already padded by the producer (TransformerASR's padded src Linear)
             x = src2d
         else:
             x = torch.zeros(src2d.shape[0], PAD_D, device=src2d.device, dtype=torch.float32)
             x[:, :d] = src2d
-        y, attns = self.sh.run(x, B, T, self.padded_pos(pos_embs, dtype), kpm_u8, dtype, need_attn)
+        y, attns = self.sh.run(x, B, T, self.padded_pos(pos_embs, dtype), kpm_u8, dtype, need_attn, pos_key=pos_key,
+                               src=src)
         return y[:, :d].contiguous(), attns

@@ -346,18 +346,31 @@ class TransformerASR(nn.Module):
             pos = self.positional_encoding.table(T, src.device, _f32)
             y, _ = self.encoder.train_run(x, B, T, pos, kpm, dtype)
             return y.view(B, T, -1)
-        kpm = self._kpm(T, wav_len, kpm, src.device)
         pos = self.positional_encoding.table(T, src.device, dtype)  # a constant table: cached in the compute dtype
+        # names the table family for the encoder's kept linear_pos projection
+        inv = self.positional_encoding.inv_freq
+        pos_key = ("RelPosEncXL", inv.data_ptr(), inv._version)
         a = _enc.to_compute(src.reshape(B * T, Fin), dtype)
         sh = self.encoder._shadow(lin.w.weight.shape[0], dtype)
+        enc = sh.sh if sh is not None else self.encoder
+        if not torch.jit.is_tracing() and enc.takes_src(Fin, dtype):
+            # the src Linear and the key padding mask run in the stack's first launch (sbk_src_ffn_proj)
+            if kpm is not None:
+                kpm = self._kpm(T, None, kpm, src.device)
+            w, b = self._padded_src(dtype) if sh is not None else (
+                lin.kernel_weight(dtype), lin.w.bias.detach() if lin.w.bias is not None else None)
+            rel = wav_len.to(device=src.device) if (wav_len is not None and kpm is None) else None
+            y, _ = (sh or self.encoder).run(None, B, T, pos, kpm, dtype, False, pos_key=pos_key, src=(a, w, b, rel))
+            return y.view(B, T, -1)
+        kpm = self._kpm(T, wav_len, kpm, src.device)
         if sh is not None:
             # d_model < 256 on the padded shadow: the src Linear writes the
             # 256-wide zero-padded input itself (no fill + copy launches)
             w, b = self._padded_src(dtype)
-            y, _ = sh.run(_enc.gemm(a, w, bias=b, out_dtype=_f32), B, T, pos, kpm, dtype, False)
+            y, _ = sh.run(_enc.gemm(a, w, bias=b, out_dtype=_f32), B, T, pos, kpm, dtype, False, pos_key=pos_key)
         else:
             x = _enc.gemm(a, lin.kernel_weight(dtype), bias=lin.w.bias.detach(), out_dtype=_f32)
-            y, _ = self.encoder.run(x, B, T, pos, kpm, dtype, False)
+            y, _ = self.encoder.run(x, B, T, pos, kpm, dtype, False, pos_key=pos_key)
         return y.view(B, T, -1)
 
     def _kpm(self, T, wav_len, kpm, device):

@@ -364,6 +364,17 @@ class PositionalwiseFeedForward(nn.Module):
         return _enc.ffn_proj(x, ln0, w1, b1, act, slope, w2, b2, alpha, next_ln, wp, post_ln=post_ln,
                              deff=self._deff)
 
+    def run_fused_src_proj(self, a, ws, bs, ln0, alpha, next_ln, wp, rel_len=None, T=None):
+        """run_fused_proj on x = a · ws^T + bs (the Linear in front of the
+        stack) in the same launch, optionally with the key padding mask:
+        returns (out fp32, next_ln(out) · wp^T bf16, mask or None)."""
+        w1, w2 = self.kernel_weights(torch.bfloat16)
+        act, slope = self.act_name()
+        b1, b2 = (lin.bias.detach() if lin.bias is not None else torch.zeros(lin.out_features, device=a.device)
+                  for lin in (self.ffn[0], self.ffn[3]))
+        return _enc.src_ffn_proj(a, ws, bs, ln0, w1, b1, act, slope, w2, b2, alpha, next_ln, wp, deff=self._deff,
+                                 rel_len=rel_len, T=T)
+
     def forward(self, x):
         shp = x.shape
         dtype = _enc.compute_dtype()
