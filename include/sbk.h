@@ -796,6 +796,30 @@ int sbk_kv_decode_cross_attn(const float* q, long long q_ld, const float* k, con
                              const int* klen, int N, int group, int H, int dh, int S, float* out, float* probs,
                              void* stream);
 
+/* sbk_kv_decode_self_attn with a key mask: the decode step of a language
+ * model that masks its padding token.  keymask (cap, N) uint8, nonzero =
+ * masked; the caller fills slot L-1 before the call.  Row n's key at j < L-1
+ * is masked by keymask[j][anc[n][j]], its new key by keymask[L-1][n].  A chunk
+ * of 64 positions may be masked whole; a (row, head) whose keys are all
+ * masked gets NaN (a softmax over -inf), without a fault.  An all-zero mask
+ * gives sbk_kv_decode_self_attn's result bit for bit.  The same requirements,
+ * and keymask not null. */
+int sbk_kv_decode_self_attn_masked(const float* q, const float* k_new, const float* v_new, long long ld, float* kc,
+                                   float* vc, int cap, const int* anc, long long anc_ld,
+                                   const unsigned char* keymask, int N, int H, int dh, int L, float* out,
+                                   void* stream);
+
+/* ---- lmfuse.hip: the LM-fusion tail of a beam-search step (fp32) -------- */
+
+/* out[n][v] = base[n][v] + w * (logits[n][v]*invT - logsumexp_v(logits[n][:]*invT)),
+ * one kernel, the row maximum subtracted.  logits (N, V) with row stride ld;
+ * base (N, V) with row stride base_ld, or null (plain scaled log-softmax); out
+ * (N, V) contiguous.  -inf / -1e20 entries of base pass through as fp32
+ * addition gives them.  Any V >= 1: a row of up to 8192 floats is read from
+ * memory once (kept in LDS), a wider one twice.  Needs ld >= V, base_ld >= V. */
+int sbk_log_softmax_fuse(const float* logits, long long ld, const float* base, long long base_ld, int N, int V,
+                         float invT, float w, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@ attention ops and the state TransformerASR.decode_step carries between steps.
     values projected once per search for the B utterances (not once per step
     for the N = B · group beam rows); a workgroup serves one (utterance, head)
     and reads each K / V row once for the beams of that utterance.
+  * kv_decode_self_attn_masked — the self-attention step with a key mask, for
+    TransformerLM.decode_step (the LM masks the keys whose token is its
+    padding index); LMDecodeState carries the mask beside the caches.
+  * log_softmax_fuse — base + w · log_softmax(logits · inv_t) in one kernel
+    (csrc/lmfuse.hip): the tail of LM fusion in the beam search.
 fp32, exact softmax; no CPU fallback.
 """
 from typing import Optional
@@ -87,6 +92,65 @@ def _(q, kv, klen, group, H, need_probs):
     return q.new_empty(N, E), q.new_empty((N, H, kv.shape[1]) if need_probs else (0,))
 
 
+@custom_op("sbk::kv_decode_self_attn_masked", mutates_args=("kc", "vc"))
+def kv_decode_self_attn_masked(qkv: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, anc: torch.Tensor,
+                               keymask: torch.Tensor, H: int, L: int) -> torch.Tensor:
+    """kv_decode_self_attn with keymask (cap, N) uint8, nonzero = masked, slot L−1 already filled: row n's key
+    at j < L−1 is masked by keymask[j][anc[n][j]], its new key by keymask[L−1][n].  A (row, head) with every
+    key masked gives NaN; an all-zero mask gives kv_decode_self_attn's result bit for bit."""
+    require_device(qkv, kc, vc, anc, keymask)
+    _f32_rows(qkv, "qkv")
+    N, E3 = qkv.shape
+    E = E3 // 3
+    if (kc.dtype != _f32 or vc.dtype != _f32 or not kc.is_contiguous() or not vc.is_contiguous()
+            or kc.shape != vc.shape or tuple(kc.shape[1:]) != (N, E) or E * 3 != E3 or E % H):
+        raise ValueError(f"kv_decode_self_attn_masked: caches {tuple(kc.shape)} / {tuple(vc.shape)} do not fit qkv "
+                         f"{tuple(qkv.shape)} with {H} heads")
+    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != N or anc.stride(1) != 1:
+        raise ValueError("kv_decode_self_attn_masked: anc must be (N, ≥ L) int32 with contiguous rows")
+    if (keymask.dtype != torch.uint8 or not keymask.is_contiguous() or keymask.dim() != 2 or keymask.shape[1] != N
+            or keymask.shape[0] < L):
+        raise ValueError(f"kv_decode_self_attn_masked: keymask must be (≥ {L}, {N}) uint8 contiguous "
+                         f"(got {keymask.dtype}, {tuple(keymask.shape)})")
+    out = torch.empty(N, E, device=qkv.device, dtype=_f32)
+    # cap: the positions both the caches and the mask hold
+    check(lib().sbk_kv_decode_self_attn_masked(ptr(qkv[:, :E]), ptr(qkv[:, E:2 * E]), ptr(qkv[:, 2 * E:]),
+                                               qkv.stride(0), ptr(kc), ptr(vc), min(kc.shape[0], keymask.shape[0]),
+                                               ptr(anc), anc.stride(0), ptr(keymask), N, H, E // H, L, ptr(out),
+                                               stream_of(qkv)), "sbk_kv_decode_self_attn_masked")
+    return out
+
+
+@kv_decode_self_attn_masked.register_fake
+def _(qkv, kc, vc, anc, keymask, H, L):
+    return qkv.new_empty(qkv.shape[0], qkv.shape[1] // 3)
+
+
+@custom_op("sbk::log_softmax_fuse", mutates_args=())
+def log_softmax_fuse(logits: torch.Tensor, base: Optional[torch.Tensor], inv_t: float, w: float) -> torch.Tensor:
+    """logits (N, V) fp32 (row stride ≥ V); base (N, V) fp32 (row stride ≥ V) | None →
+    base + w · log_softmax(logits · inv_t, dim=−1) (N, V), one kernel (csrc/lmfuse.hip)."""
+    require_device(logits, base)
+    _f32_rows(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError(f"log_softmax_fuse: logits must be (N, V) (got {tuple(logits.shape)})")
+    N, V = logits.shape
+    if base is not None:
+        _f32_rows(base, "base")
+        if base.shape != logits.shape:
+            raise ValueError(f"log_softmax_fuse: base {tuple(base.shape)} != logits {tuple(logits.shape)}")
+    out = torch.empty(N, V, device=logits.device, dtype=_f32)
+    check(lib().sbk_log_softmax_fuse(ptr(logits), logits.stride(0), ptr(base), base.stride(0) if base is not None else 0,
+                                     N, V, float(inv_t), float(w), ptr(out), stream_of(logits)),
+          "sbk_log_softmax_fuse")
+    return out
+
+
+@log_softmax_fuse.register_fake
+def _(logits, base, inv_t, w):
+    return logits.new_empty(logits.shape)
+
+
 class DecodeState:
     """What TransformerASR.decode_step keeps between steps: per decoder layer
     the cross-attention [K | V] (B, S, 2E), computed once, and the
@@ -137,3 +201,41 @@ class DecodeState:
         """New row n continues old row index[n]: the ancestry rows move, the caches stay."""
         self.anc = self.anc.index_select(0, index)
         return self
+
+
+class LMDecodeState(DecodeState):
+    """What TransformerLM.decode_step keeps between steps: DecodeState without
+    cross-attention — per encoder layer the self-attention caches
+    (cap, N, E), the ancestry table anc (N, cap) — plus keymask (cap, N)
+    uint8, 1 where the token a row fed at that position was the padding
+    index.  It is indexed like the caches (position, then the row that wrote
+    it), so a beam permutation moves anc only."""
+
+    def __init__(self, rows, layers, d_model, nhead, device):
+        self.cross_kv = []
+        self.klen = None
+        self.group = 1
+        self.nhead = nhead
+        self.rows = rows
+        self.d_model = d_model
+        self.device = device
+        self.capacity = INITIAL_CAPACITY
+        self.steps = 0
+        self.kc = [self._cache(self.capacity) for _ in range(layers)]
+        self.vc = [self._cache(self.capacity) for _ in range(layers)]
+        self.anc = torch.zeros(rows, self.capacity, device=device, dtype=torch.int32)
+        self.keymask = torch.zeros(self.capacity, rows, device=device, dtype=torch.uint8)
+        self._row_ids = torch.arange(rows, device=device, dtype=torch.int32)
+
+    def _grow(self):
+        old = self.capacity
+        super()._grow()
+        keymask = torch.zeros(self.capacity, self.rows, device=self.device, dtype=torch.uint8)
+        keymask[:old] = self.keymask
+        self.keymask = keymask
+
+    def begin_step(self, masked):
+        """DecodeState.begin_step, and slot L−1 of keymask ← masked (N) bool."""
+        L = super().begin_step()
+        self.keymask[L - 1] = masked
+        return L

@@ -131,6 +131,9 @@ SIGNATURES = {
     # kvdec.hip (incremental transformer decoding: self-attention over the cache, cross-attention)
     "sbk_kv_decode_self_attn": [_vp, _vp, _vp, _ll, _vp, _vp, _i, _vp, _ll, _i, _i, _i, _i, _vp, _vp],
     "sbk_kv_decode_cross_attn": [_vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "sbk_kv_decode_self_attn_masked": [_vp, _vp, _vp, _ll, _vp, _vp, _i, _vp, _ll, _vp, _i, _i, _i, _i, _vp, _vp],
+    # lmfuse.hip (LM fusion: base + w * log_softmax(logits / T))
+    "sbk_log_softmax_fuse": [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _vp],
     # attention.hip
     "sbk_relpos_attention": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],

@@ -45,10 +45,22 @@ __device__ __forceinline__ float dot4(float4 a, float4 b, float s) {
 // 16-byte loads against q in LDS; the probabilities and the clamped ancestors
 // go through LDS; P*V: the lane's two columns over the chunk's value rows
 // (one coalesced run per position).  Online softmax across chunks.
+//
+// MASKED: keymask (cap, N) bytes, nonzero = the key is masked (the language
+// model's padding mask: the token at that position is pad_idx).  Row n's key
+// at j < L-1 is masked by keymask[j][anc[n][j]], its new key by
+// keymask[L-1][n]; a masked score is -inf.  A chunk, or every chunk so far,
+// may then hold no finite score: the exponentials are taken against 0 while
+// the running maximum is still -inf, so they are exp(-inf) = 0, never
+// exp(-inf - -inf).  A (row, head) with every key masked ends with l = 0 and
+// writes 0 / 0 = NaN, as a softmax over an all -inf row does.  With no byte
+// set the arithmetic is the unmasked kernel's, operation for operation.
+template <bool MASKED>
 __global__ void __launch_bounds__(64)
     kv_self_kernel(const float* __restrict__ q, const float* __restrict__ k_new, const float* __restrict__ v_new,
                    long long ld, float* __restrict__ kc, float* __restrict__ vc, const int* __restrict__ anc,
-                   long long anc_ld, int N, int H, int dh, int L, float scale, float* __restrict__ out) {
+                   long long anc_ld, const uint8_t* __restrict__ keymask, int N, int H, int dh, int L, float scale,
+                   float* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) float qs[kDhMax];
   __shared__ float ps[64];
   __shared__ int an[64];
@@ -90,10 +102,17 @@ __global__ void __launch_bounds__(64)
       for (int i = 0; i < dh / 4; ++i) d = dot4(*reinterpret_cast<const float4*>(qs + 4 * i), ld4(kr + 4 * i), d);
       s = d * scale;
     }
+    if constexpr (MASKED) {
+      if (j < L && keymask[(long long)j * N + a]) s = -INFINITY;  // j = L-1: a = n
+    }
     an[lane] = a;
-    const float m_new = fmaxf(m, wave_max(s));  // finite: every chunk holds a position < L
-    const float p = (j < L) ? expf(s - m_new) : 0.f;
-    const float alpha = expf(m - m_new);  // first chunk: exp(-inf) = 0
+    float m_new = fmaxf(m, wave_max(s));  // unmasked: finite, every chunk holds a position < L
+    float m_ref = m_new;                  // what the exponentials are taken against
+    if constexpr (MASKED) {
+      if (m_new == -INFINITY) m_ref = 0.f;  // nothing unmasked yet: p = alpha = exp(-inf) = 0
+    }
+    const float p = (j < L) ? expf(s - m_ref) : 0.f;
+    const float alpha = expf(m - m_ref);  // first chunk: exp(-inf) = 0
     l = l * alpha + wave_sum(p);
     acc0 *= alpha;
     acc1 *= alpha;
@@ -283,8 +302,29 @@ SBK_API int sbk_kv_decode_self_attn(const float* q, const float* k_new, const fl
   const long long E = (long long)H * dh;
   if (ld < E || ld % 4 != 0 || anc_ld < L || (long long)N * H > INT_MAX || E > INT_MAX) return SBK_ERR_ARG;
   if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(kc) || !aligned16(vc)) return SBK_ERR_ARG;
-  hipLaunchKernelGGL(kv_self_kernel, dim3(N * H), dim3(64), 0, (hipStream_t)stream, q, k_new, v_new, ld, kc, vc, anc,
-                     anc_ld, N, H, dh, L, 1.f / sqrtf((float)dh), out);
+  hipLaunchKernelGGL(kv_self_kernel<false>, dim3(N * H), dim3(64), 0, (hipStream_t)stream, q, k_new, v_new, ld, kc, vc,
+                     anc, anc_ld, nullptr, N, H, dh, L, 1.f / sqrtf((float)dh), out);
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
+// The same step with a key mask (the decode step of a language model that
+// masks its padding token): keymask (cap, N) uint8, nonzero = masked, slot
+// L-1 filled by the caller before the call.  Row n's key at j < L-1 is masked
+// by keymask[j][anc[n][j]], its new key by keymask[L-1][n].  A (row, head)
+// whose keys are all masked gets NaN.  With an all-zero mask the result is
+// bit-equal to sbk_kv_decode_self_attn.
+SBK_API int sbk_kv_decode_self_attn_masked(const float* q, const float* k_new, const float* v_new, long long ld,
+                                           float* kc, float* vc, int cap, const int* anc, long long anc_ld,
+                                           const unsigned char* keymask, int N, int H, int dh, int L, float* out,
+                                           void* stream) {
+  if (!q || !k_new || !v_new || !kc || !vc || !anc || !keymask || !out) return SBK_ERR_ARG;
+  if (N <= 0 || H <= 0 || dh <= 0 || L <= 0 || dh % 4 != 0 || dh > kDhMax || L > cap) return SBK_ERR_ARG;
+  const long long E = (long long)H * dh;
+  if (ld < E || ld % 4 != 0 || anc_ld < L || (long long)N * H > INT_MAX || E > INT_MAX) return SBK_ERR_ARG;
+  if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(kc) || !aligned16(vc)) return SBK_ERR_ARG;
+  hipLaunchKernelGGL(kv_self_kernel<true>, dim3(N * H), dim3(64), 0, (hipStream_t)stream, q, k_new, v_new, ld, kc, vc,
+                     anc, anc_ld, keymask, N, H, dh, L, 1.f / sqrtf((float)dh), out);
   SBK_CHECK_LAUNCH();
   return 0;
 }

@@ -27,10 +27,17 @@ newest token only, against a key/value cache and cross-attention K / V
 projected once for the un-inflated utterances (csrc/kvdec.hip) — and a beam
 permutation moves the cache's (N, L) ancestry table, not the cache.  Otherwise,
 like the reference, every step re-decodes the whole prefix.
+LM fusion has the same switch, USE_LM_KV_CACHE (off by default): with
+lm_modules a TransformerLM that decode_step_supported() takes, the LM step
+embeds the newest token only against the LM's own key/value cache, and
+log_probs + lm_weight · log_softmax(logits / temperature_lm) is one kernel
+(csrc/lmfuse.hip) through the _add_lm_scores hook.  With any other lm_modules
+the LM runs on the whole prefix, as in the reference.
 """
 import torch
 
-from .. import _kvdec  # noqa: F401  (registers the decode-step ops the cached search runs)
+from .. import _kvdec  # registers the decode-step ops the cached search runs
+from ..lobes.models.transformer.TransformerLM import TransformerLM
 from .ctc import CTCPrefixScorer
 
 
@@ -226,7 +233,7 @@ class S2SBeamSearcher(S2SBaseSearcher):
                                                                  fill_value=self.minus_inf)
             if self.lm_weight > 0:
                 lm_log_probs, lm_memory = self.lm_forward_step(inp_tokens, lm_memory)
-                log_probs = log_probs + self.lm_weight * lm_log_probs
+                log_probs = self._add_lm_scores(log_probs, lm_log_probs)
             if self.ctc_weight > 0:
                 g = alived_seq
                 log_probs[:, self.blank_index] = self.minus_inf
@@ -282,6 +289,10 @@ class S2SBeamSearcher(S2SBaseSearcher):
             return predictions, topk_scores, log_probs
         return predictions, topk_scores
 
+    def _add_lm_scores(self, log_probs, lm_log_probs):
+        """LM fusion (seq2seq.py:756-760): what lm_forward_step returned, weighted, onto the step's scores."""
+        return log_probs + self.lm_weight * lm_log_probs
+
     def ctc_forward_step(self, x):
         logits = self.ctc_fc(x)
         return self.softmax(logits)
@@ -316,6 +327,8 @@ class S2STransformerBeamSearch(S2SBeamSearcher):
     # incremental decoding through TransformerASR.decode_step; the constructor
     # is the reference's, so this is an attribute (as Conformer.USE_CONV_CHAIN)
     USE_KV_CACHE = False
+    # the same for LM fusion: lm_modules a TransformerLM that takes decode_step
+    USE_LM_KV_CACHE = False
 
     def __init__(self, modules, temperature=1.0, temperature_lm=1.0, **kwargs):
         super().__init__(**kwargs)
@@ -340,7 +353,13 @@ class S2STransformerBeamSearch(S2SBeamSearcher):
             return memory.permute(index)
         return torch.index_select(memory, dim=0, index=index)
 
+    def _lm_kv_cache(self):
+        return (self.USE_LM_KV_CACHE and isinstance(self.lm_modules, TransformerLM)
+                and self.lm_modules.decode_step_supported())
+
     def permute_lm_mem(self, memory, index):
+        if self._lm_kv_cache():
+            return memory.permute(index)
         return torch.index_select(memory, dim=0, index=index)
 
     def forward_step(self, inp_tokens, memory, enc_states, enc_lens):
@@ -358,12 +377,26 @@ class S2STransformerBeamSearch(S2SBeamSearcher):
         return prob_dist[:, -1, :], memory, attn
 
     def lm_forward_step(self, inp_tokens, memory):
+        if self._lm_kv_cache():
+            # memory is the LM's decode state; what is returned are the raw
+            # logits of the newest position: _add_lm_scores takes them
+            if not next(self.lm_modules.parameters()).is_cuda:
+                self.lm_modules.to(inp_tokens.device)
+            if memory is None:
+                memory = self.lm_modules.init_decode_state(inp_tokens.shape[0])
+            return self.lm_modules.decode_step(inp_tokens, memory), memory
         memory = _update_mem(inp_tokens, memory)
         if not next(self.lm_modules.parameters()).is_cuda:
             self.lm_modules.to(inp_tokens.device)
         logits = self.lm_modules(memory)
         log_probs = self.softmax(logits / self.temperature_lm)
         return log_probs[:, -1, :], memory
+
+    def _add_lm_scores(self, log_probs, lm_log_probs):
+        if self._lm_kv_cache():
+            # lm_log_probs are the logits: temperature, log-softmax, weight and add in one kernel
+            return _kvdec.log_softmax_fuse(lm_log_probs, log_probs, 1.0 / self.temperature_lm, self.lm_weight)
+        return super()._add_lm_scores(log_probs, lm_log_probs)
 
 
 def batch_filter_seq2seq_output(prediction, eos_id=-1):
