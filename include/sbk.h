@@ -820,6 +820,66 @@ int sbk_kv_decode_self_attn_masked(const float* q, const float* k_new, const flo
 int sbk_log_softmax_fuse(const float* logits, long long ld, const float* base, long long base_ld, int N, int V,
                          float invT, float w, float* out, void* stream);
 
+/* ---- w2vloss.hip: the wav2vec 2.0 pre-training objective (fp32) --------- */
+
+/* Contrastive loss forward (losses.py:1198-1251).  x, y (R, C) contiguous.
+ * Row r is scored against N + 1 candidates: y[r], then either
+ * negs[r*s_row + (j-1)*s_neg ...] (float mode: idx null; strides in floats,
+ * unit column stride) or y[idx[r*N + j-1]] (index mode: negs null; idx int32,
+ * clamped to [0, R)).  logits (R, N+1) = cos / temp with torch's
+ * cosine_similarity formula (eps 1e-8), -inf where a negative equals y[r]
+ * element for element; rowloss (R) = logsumexp - logits[:, 0]; correct (R) =
+ * 1.0 where candidate 0 is the row maximum; aux (R, 2) = (|x_r|, logsumexp).
+ * Any C, N >= 1 with (2*roundup4(C) + N + 17) floats <= 64 KB; 16-byte row
+ * loads when C % 4 == 0 and the pointers and strides allow.  R, C, N <= 0,
+ * temp <= 0, both or neither of negs / idx: 1001. */
+int sbk_w2v_contrast_fwd(const float* x, const float* y, const float* negs, const int* idx, int R, int C, int N,
+                         long long s_row, long long s_neg, float temp, float* logits, float* rowloss, float* correct,
+                         float* aux, void* stream);
+
+/* Backward wrt x, from the forward's logits and aux; go (R) the gradient of
+ * rowloss.  dx (R, C).  Float mode also writes dnegs (R, N, C) — the gradient
+ * of candidate j of row r at [r][j-1] — and the positive's term dy (R, C);
+ * either may be null.  Index mode writes the per-pair coefficients ca, cb
+ * (R, N+1) that sbk_w2v_contrast_bwd_y consumes.  -inf candidates get zeros.
+ * Needs (6*roundup4(C) + 16) floats <= 64 KB. */
+int sbk_w2v_contrast_bwd_x(const float* x, const float* y, const float* negs, const int* idx, const float* logits,
+                           const float* aux, const float* go, int R, int C, int N, long long s_row, long long s_neg,
+                           float temp, float* dx, float* dy, float* dnegs, float* ca, float* cb, void* stream);
+
+/* Index mode's dy (R, C): order (R*(N+1)) int64 = the pair ids r*(N+1)+j
+ * sorted stably by the row of y they reference (pair (r, 0) references r),
+ * offs (R+1) int64 = each row's list start.  A gather per target row in list
+ * order: no atomics, bitwise reproducible. */
+int sbk_w2v_contrast_bwd_y(const float* x, const float* y, const long long* order, const long long* offs,
+                           const float* ca, const float* cb, int R, int C, int N, float* dy, void* stream);
+
+/* Rows of the partial-sum buffer sbk_gumbel_vq_fwd fills (one per wave). */
+int sbk_gumbel_vq_parts(int Rq, int G);
+
+/* GumbelVectorQuantizer after the projection (quantisers.py:86-122).  logits
+ * (Rq*G, V); gumbels the same shape (training) or null (eval); vars
+ * (ncodes = G*V, D).  Writes out (Rq, G*D) = the chosen vars rows side by
+ * side; codes (Rq*G) int32 = g*V + chosen index — argmax of logits + gumbels
+ * in training, of logits in eval, lowest index on a tie; counts (ncodes)
+ * int32, zeroed by the caller, += 1 at g*V + argmax(logits); part
+ * (sbk_gumbel_vq_parts, ncodes) partial column sums of softmax(logits), to be
+ * summed over rows by the caller; ysoft (Rq*G, V) = softmax((logits +
+ * gumbels) / tau) in training, null in eval.  Needs 4*ncodes floats <= 64 KB.
+ * G*V != ncodes, a size <= 0, tau <= 0: 1001. */
+int sbk_gumbel_vq_fwd(const float* logits, const float* gumbels, float tau, int Rq, int G, int V, const float* vars,
+                      int ncodes, int D, float* out, int* codes, int* counts, float* part, float* ysoft, void* stream);
+
+/* Backward.  dout (Rq, G*D); gpsum (ncodes) the gradient of the summed
+ * softmax columns; order (Rq*G) int64 = item ids sorted stably by code, offs
+ * (ncodes+1) int64.  dlogits (Rq*G, V) = [ysoft given: the straight-through
+ * term ysoft*(gy - <gy, ysoft>)/tau, gy[v] = <dout_g, vars[gV+v]>] +
+ * p*(gpsum - <p, gpsum>), p = softmax(logits); dvars (ncodes, D) = per code
+ * the sum of dout_g over its items in list order. */
+int sbk_gumbel_vq_bwd(const float* dout, const float* vars, const float* logits, const float* ysoft,
+                      const float* gpsum, float tau, const long long* order, const long long* offs, int Rq, int G,
+                      int V, int ncodes, int D, float* dlogits, float* dvars, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,14 @@ SIGNATURES = {
     "sbk_kv_decode_self_attn_masked": [_vp, _vp, _vp, _ll, _vp, _vp, _i, _vp, _ll, _vp, _i, _i, _i, _i, _vp, _vp],
     # lmfuse.hip (LM fusion: base + w * log_softmax(logits / T))
     "sbk_log_softmax_fuse": [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _vp],
+    # w2vloss.hip (wav2vec 2.0 objective: contrastive loss, Gumbel vector quantiser)
+    "sbk_w2v_contrast_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _f, _vp, _vp, _vp, _vp, _vp],
+    "sbk_w2v_contrast_bwd_x": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _f, _vp, _vp, _vp, _vp, _vp,
+                               _vp],
+    "sbk_w2v_contrast_bwd_y": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "sbk_gumbel_vq_parts": [_i, _i],
+    "sbk_gumbel_vq_fwd": [_vp, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sbk_gumbel_vq_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     # attention.hip
     "sbk_relpos_attention": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],

@@ -4,7 +4,11 @@ LayerNorm / activation / MXFP8 quantisation kernel and the MXFP8 GEMM.
 
 MXFP8 tensors travel as two tensors: e4m3 bytes (uint8, (M, K)) and one
 E8M0 scale byte per 32 consecutive K elements (uint8, (M, K/32)).  `MX`
-bundles them for the module code.  No op has a CPU path."""
+bundles them for the module code.  No op has a CPU path.
+
+Second half: the pre-training objective's ops over csrc/w2vloss.hip — the
+contrastive loss (float negatives or row indices, with its backward) and the
+Gumbel vector quantiser after the projection (with its backward)."""
 import functools
 from typing import NamedTuple, Optional
 
@@ -200,3 +204,222 @@ def add_posenc(x: torch.Tensor, pe: torch.Tensor, T: int) -> None:
 @add_posenc.register_fake
 def _(x, pe, T):
     return None
+
+
+# ---------------------------------------------------------------------------
+# The pre-training objective (csrc/w2vloss.hip): contrastive loss and the
+# Gumbel vector quantiser.  fp32 device tensors; no CPU path.
+_i32, _i64 = torch.int32, torch.int64
+
+
+def _neg_strides(negs):
+    """(row stride, negative stride) in floats of negs (N, B, T, C) whose
+    (B, T) dims collapse to one row index (checked by the caller)."""
+    return (negs.stride(2) if negs.shape[2] > 1 else negs.stride(1)), negs.stride(0)
+
+
+@custom_op("sbk::w2v_contrast", mutates_args=())
+def contrast(x: torch.Tensor, y: torch.Tensor, negs: Optional[torch.Tensor], idx: Optional[torch.Tensor],
+             order: Optional[torch.Tensor], offs: Optional[torch.Tensor],
+             temp: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """x, y (R, C) fp32; negs (N, B, T, C) fp32 or idx (R, N) int32 (exactly
+    one).  Returns (rowloss (R), correct (R), logits (R, N+1), aux (R, 2)).
+    order / offs: idx's inverse index, only carried for the backward."""
+    R, C = x.shape
+    N = negs.shape[0] if negs is not None else idx.shape[1]
+    logits = torch.empty(R, N + 1, device=x.device, dtype=_f32)
+    rowloss = torch.empty(R, device=x.device, dtype=_f32)
+    correct = torch.empty(R, device=x.device, dtype=_f32)
+    aux = torch.empty(R, 2, device=x.device, dtype=_f32)
+    s_row, s_neg = _neg_strides(negs) if negs is not None else (0, 0)
+    check(lib().sbk_w2v_contrast_fwd(ptr(x), ptr(y), ptr(negs), ptr(idx), R, C, N, s_row, s_neg, float(temp),
+                                     ptr(logits), ptr(rowloss), ptr(correct), ptr(aux), stream_of(x)),
+          "sbk_w2v_contrast_fwd")
+    return rowloss, correct, logits, aux
+
+
+@contrast.register_fake
+def _(x, y, negs, idx, order, offs, temp):
+    R = x.shape[0]
+    N = negs.shape[0] if negs is not None else idx.shape[1]
+    return x.new_empty(R), x.new_empty(R), x.new_empty(R, N + 1), x.new_empty(R, 2)
+
+
+@custom_op("sbk::w2v_contrast_grad", mutates_args=())
+def contrast_grad(x: torch.Tensor, y: torch.Tensor, negs: Optional[torch.Tensor], idx: Optional[torch.Tensor],
+                  order: Optional[torch.Tensor], offs: Optional[torch.Tensor], logits: torch.Tensor,
+                  aux: torch.Tensor, go: torch.Tensor, temp: float, need_dy: bool,
+                  need_dnegs: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx (R, C), dy (R, C), dnegs (R, N, C)); a gradient that is not needed
+    (or, for dnegs, does not exist in index mode) comes back empty."""
+    R, C = x.shape
+    N = logits.shape[1] - 1
+    dev = x.device
+    dx = torch.empty(R, C, device=dev, dtype=_f32)
+    dy = torch.empty(R, C if need_dy else 0, device=dev, dtype=_f32)
+    L = lib()
+    if idx is None:
+        dnegs = torch.empty(R, N, C if need_dnegs else 0, device=dev, dtype=_f32)
+        s_row, s_neg = _neg_strides(negs)
+        check(L.sbk_w2v_contrast_bwd_x(ptr(x), ptr(y), ptr(negs), None, ptr(logits), ptr(aux), ptr(go), R, C, N, s_row,
+                                       s_neg, float(temp), ptr(dx), ptr(dy) if need_dy else None,
+                                       ptr(dnegs) if need_dnegs else None, None, None, stream_of(x)),
+              "sbk_w2v_contrast_bwd_x")
+        return dx, dy, dnegs
+    ca = torch.empty(R, N + 1, device=dev, dtype=_f32)
+    cb = torch.empty(R, N + 1, device=dev, dtype=_f32)
+    check(L.sbk_w2v_contrast_bwd_x(ptr(x), ptr(y), None, ptr(idx), ptr(logits), ptr(aux), ptr(go), R, C, N, 0, 0,
+                                   float(temp), ptr(dx), None, None, ptr(ca), ptr(cb), stream_of(x)),
+          "sbk_w2v_contrast_bwd_x")
+    if need_dy:
+        check(L.sbk_w2v_contrast_bwd_y(ptr(x), ptr(y), ptr(order), ptr(offs), ptr(ca), ptr(cb), R, C, N, ptr(dy),
+                                       stream_of(x)), "sbk_w2v_contrast_bwd_y")
+    return dx, dy, torch.empty(R, N, 0, device=dev, dtype=_f32)
+
+
+@contrast_grad.register_fake
+def _(x, y, negs, idx, order, offs, logits, aux, go, temp, need_dy, need_dnegs):
+    R, C = x.shape
+    N = logits.shape[1] - 1
+    return (x.new_empty(R, C), x.new_empty(R, C if need_dy else 0),
+            x.new_empty(R, N, C if need_dnegs and idx is None else 0))
+
+
+def _contrast_setup(ctx, inputs, output):
+    x, y, negs, idx, order, offs, temp = inputs
+    ctx.save_for_backward(x, y, negs, idx, order, offs, output[2], output[3])
+    ctx.temp = temp
+
+
+def _contrast_backward(ctx, g_loss, g_correct, g_logits, g_aux):
+    x, y, negs, idx, order, offs, logits, aux = ctx.saved_tensors
+    need_dy = ctx.needs_input_grad[1]
+    need_dn = negs is not None and ctx.needs_input_grad[2]
+    if need_dy and idx is not None and order is None:
+        raise RuntimeError("sbk::w2v_contrast: y requires grad in index mode but no inverse index was passed")
+    go = g_loss.detach().to(_f32).contiguous()
+    dx, dy, dn = contrast_grad(x, y, negs, idx, order, offs, logits, aux, go, ctx.temp, need_dy, need_dn)
+    if need_dn:  # (R, N, C) -> the (N, B, T, C) view of the same memory
+        dn = dn.view(negs.shape[1], negs.shape[2], negs.shape[0], negs.shape[3]).permute(2, 0, 1, 3)
+    return dx, dy if need_dy else None, dn if need_dn else None, None, None, None, None
+
+
+contrast.register_autograd(_contrast_backward, setup_context=_contrast_setup)
+
+
+def inverse_index(idx):
+    """idx (R, N) int32 rows of y referenced by row r's negatives → (order,
+    offs): the pair ids r·(N+1) + j (j = 0 the positive, which references row
+    r) sorted stably by referenced row, and each row's list start (R + 1).
+    Device-side torch, once per forward."""
+    R, N = idx.shape
+    keys = torch.cat([torch.arange(R, device=idx.device, dtype=_i32)[:, None], idx], 1).reshape(-1)
+    skeys, order = torch.sort(keys, stable=True)
+    offs = torch.searchsorted(skeys, torch.arange(R + 1, device=idx.device, dtype=_i32))
+    return order.contiguous(), offs.to(_i64).contiguous()
+
+
+def contrastive_rows(x, y, negs, temp):
+    """Per-row contrastive loss (R,), correct flags (R,) and logits (R, N+1)
+    of x, y (B, T, C) and negs — float (N, B, T, C) or integer (B, T·N) flat
+    row indices into y.view(-1, C).  Differentiable wrt x, y and float negs."""
+    require_device(x, y, negs)
+    if x.dim() != 3 or y.shape != x.shape:
+        raise ValueError(f"expected x and y of one (B, T, C) shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    B, T, C = x.shape
+    R = B * T
+    x2 = x.float().reshape(R, C).contiguous()
+    y2 = y.float().reshape(R, C).contiguous()
+    if negs.is_floating_point():
+        if negs.dim() != 4 or tuple(negs.shape[1:]) != (B, T, C):
+            raise ValueError(f"expected negs (N, {B}, {T}, {C}), got {tuple(negs.shape)}")
+        negs = negs.float()
+        if negs.stride(3) != 1 or (B > 1 and T > 1 and negs.stride(1) != T * negs.stride(2)):
+            negs = negs.contiguous()
+        return contrast(x2, y2, negs, None, None, None, float(temp))[:3]
+    if negs.dim() != 2 or negs.shape[0] != B or negs.shape[1] % T:
+        raise ValueError(f"expected integer negs (B, T*N) = ({B}, {T}*N), got {tuple(negs.shape)}")
+    idx = negs.reshape(R, -1).clamp(0, R - 1).to(_i32).contiguous()
+    order = offs = None
+    if torch.is_grad_enabled() and y2.requires_grad:
+        order, offs = inverse_index(idx)
+    return contrast(x2, y2, None, idx, order, offs, float(temp))[:3]
+
+
+@custom_op("sbk::gumbel_vq", mutates_args=())
+def gumbel_vq(logits: torch.Tensor, gumbels: Optional[torch.Tensor], vars: torch.Tensor, tau: float,
+              groups: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """logits (Rq·G, V) fp32, gumbels the same shape (training) or None
+    (eval), vars (G·V, D).  Returns (out (Rq, G·D), codes (Rq·G) int32 =
+    g·V + chosen, counts (G·V) int32 of argmax(logits), psum (G·V) column
+    sums of softmax(logits), ysoft (training; empty in eval))."""
+    M, V = logits.shape
+    G = int(groups)
+    Rq = M // G
+    ncodes, D = vars.shape
+    dev = logits.device
+    L = lib()
+    out = torch.empty(Rq, G * D, device=dev, dtype=_f32)
+    codes = torch.empty(M, device=dev, dtype=_i32)
+    counts = torch.zeros(ncodes, device=dev, dtype=_i32)
+    nparts = int(L.sbk_gumbel_vq_parts(Rq, G))
+    part = torch.empty(max(nparts, 1), ncodes, device=dev, dtype=_f32)
+    ysoft = torch.empty(M, V, device=dev, dtype=_f32) if gumbels is not None else torch.empty(0, device=dev, dtype=_f32)
+    check(L.sbk_gumbel_vq_fwd(ptr(logits), ptr(gumbels), float(tau), Rq, G, V, ptr(vars), ncodes, D, ptr(out),
+                              ptr(codes), ptr(counts), ptr(part), ptr(ysoft) if gumbels is not None else None,
+                              stream_of(logits)), "sbk_gumbel_vq_fwd")
+    psum = torch.empty(ncodes, device=dev, dtype=_f32)
+    check(L.sbk_colsum(ptr(part), nparts, ncodes, ptr(psum), 0, stream_of(logits)), "sbk_colsum")
+    return out, codes, counts, psum, ysoft
+
+
+@gumbel_vq.register_fake
+def _(logits, gumbels, vars, tau, groups):
+    M, V = logits.shape
+    ncodes, D = vars.shape
+    return (logits.new_empty(M // groups, groups * D), logits.new_empty(M, dtype=_i32),
+            logits.new_empty(ncodes, dtype=_i32), logits.new_empty(ncodes),
+            logits.new_empty(M, V) if gumbels is not None else logits.new_empty(0))
+
+
+@custom_op("sbk::gumbel_vq_grad", mutates_args=())
+def gumbel_vq_grad(dout: torch.Tensor, gpsum: torch.Tensor, logits: torch.Tensor, vars: torch.Tensor,
+                   codes: torch.Tensor, ysoft: Optional[torch.Tensor], tau: float,
+                   groups: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dlogits (Rq·G, V), dvars (G·V, D)): the straight-through term where
+    ysoft is given, the gradient of the softmax column sums, and dout summed
+    per chosen code over a stable sort of the codes."""
+    M, V = logits.shape
+    G = int(groups)
+    ncodes, D = vars.shape
+    dev = logits.device
+    skeys, order = torch.sort(codes, stable=True)
+    offs = torch.searchsorted(skeys, torch.arange(ncodes + 1, device=dev, dtype=_i32)).to(_i64)
+    dlogits = torch.empty(M, V, device=dev, dtype=_f32)
+    dvars = torch.empty(ncodes, D, device=dev, dtype=_f32)
+    check(lib().sbk_gumbel_vq_bwd(ptr(dout), ptr(vars), ptr(logits), ptr(ysoft), ptr(gpsum), float(tau), ptr(order),
+                                  ptr(offs), M // G, G, V, ncodes, D, ptr(dlogits), ptr(dvars), stream_of(logits)),
+          "sbk_gumbel_vq_bwd")
+    return dlogits, dvars
+
+
+@gumbel_vq_grad.register_fake
+def _(dout, gpsum, logits, vars, codes, ysoft, tau, groups):
+    return torch.empty_like(logits), torch.empty_like(vars)
+
+
+def _vq_setup(ctx, inputs, output):
+    logits, gumbels, vars, tau, groups = inputs
+    ctx.training = gumbels is not None
+    ctx.save_for_backward(logits, vars, output[1], output[4])
+    ctx.tau, ctx.groups = tau, groups
+
+
+def _vq_backward(ctx, g_out, g_codes, g_counts, g_psum, g_ysoft):
+    logits, vars, codes, ysoft = ctx.saved_tensors
+    dlogits, dvars = gumbel_vq_grad(g_out.detach().float().contiguous(), g_psum.detach().float().contiguous(), logits,
+                                    vars, codes, ysoft if ctx.training else None, ctx.tau, ctx.groups)
+    return dlogits, None, dvars, None, None
+
+
+gumbel_vq.register_autograd(_vq_backward, setup_context=_vq_setup)

@@ -15,16 +15,28 @@ padding "valid", LayerNorm over channels, GELU; B x 15 s → 748 frames):
   closing nn.LayerNorm      sbk_ln_act
 State-dict keys match the reference (extractor.convblock_i.convs.conv_0.conv.
 weight, .norm_0.norm.{weight,bias}, norm.{weight,bias}).
+
+The pre-training side of the recipe: W2VTargetQuantiser (:109-152, the HIP
+GumbelVectorQuantizer + a Linear), compute_mask (:238-302) and
+w2v_mask_collate_fn (:333-382) on the host with the reference's random draws
+in the reference's order, sample_negatives (:305-330) and
+sample_negative_indices — the same draw returned as flat row indices, which
+nnet.losses.ContrastiveLoss takes in place of the materialised negatives.
 """
+import random
+
+import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import _enc
 from ... import _autograd as A
 from ...nnet.normalization import LayerNorm
+from ...nnet.quantisers import GumbelVectorQuantizer
 from .transformer.Transformer import PositionalEncoding, TransformerEncoder, _mode
 
-__all__ = ["W2VLatentExtractor", "EncoderWrapper"]
+__all__ = ["W2VLatentExtractor", "EncoderWrapper", "W2VTargetQuantiser", "compute_mask", "sample_negatives",
+           "sample_negative_indices", "w2v_mask_collate_fn"]
 
 _f32, _bf16 = torch.float32, torch.bfloat16
 
@@ -275,3 +287,103 @@ class EncoderWrapper(nn.Module):
         B, T, C = latents.shape
         y = self.embed(latents.float().reshape(B * T, C).contiguous(), B, T, wav_lens, padding_mask)
         return {"embeddings": y.view(B, T, -1)}
+
+
+class W2VTargetQuantiser(nn.Module):
+    """wav2vec.py:109-152: GumbelVectorQuantizer with 2 groups, then a Linear
+    on the quantised vectors.  Returns (targets, meta) with meta keys
+    diversity_loss, code_perplex, prob_perplex, num_vars, temp."""
+
+    def __init__(self, in_dim=512, out_dim=256, quantiser=GumbelVectorQuantizer, num_vars=320,
+                 temperature_decay=(2.0, 0.25, 0.999995,)):
+        super().__init__()
+        self.quantiser = quantiser(in_dim, num_vars, temperature_decay, 2, out_dim)
+        self.proj = nn.Linear(out_dim, out_dim)
+        self._wc = _enc.WeightCache()
+
+    def forward(self, x):
+        q = self.quantiser(x)
+        B, T, D = q["x"].shape
+        targets = A.linear(q["x"].reshape(B * T, D), self.proj.weight, self.proj.bias, _enc.compute_dtype(), self._wc,
+                           "tq_proj").view(B, T, -1)
+        num_vars, prob_perplex = q["num_vars"], q["prob_perplex"]
+        meta = {
+            "diversity_loss": (num_vars - prob_perplex) / num_vars,
+            "code_perplex": q["code_perplexity"],
+            "prob_perplex": prob_perplex,
+            "num_vars": num_vars,
+            "temp": q["temp"],
+        }
+        return targets, meta
+
+
+def compute_mask(shape, sample_lens, mask_prob, mask_length):
+    """wav2vec.py:238-302: boolean (B, T) numpy mask of about mask_prob of
+    the shortest sample, in spans of mask_length, the same count for every
+    sample and none in the padding.  Host code drawing as the reference does
+    — one random.random(), then per sample one np.random.choice of span
+    starts, then per short sample one np.random.choice of fill-ins — so equal
+    seeds give the reference's mask."""
+    bs, padded_len = shape
+    num_mask = int(mask_prob * min(sample_lens) / float(mask_length) + random.random() + 1)
+    spans = np.arange(mask_length)
+    picked = []
+    for i in range(bs):
+        starts = np.random.choice(sample_lens[i] - mask_length, num_mask, replace=False)
+        frames = (np.asarray(starts)[:, None] + spans[None, :]).reshape(-1)
+        picked.append(np.unique(frames[frames < sample_lens[i]]))
+    mask = np.full((bs, padded_len), False)
+    want = num_mask * mask_length
+    for i, frames in enumerate(picked):
+        if len(frames) < want:  # overlapping spans: top up with frames not yet chosen
+            free = np.delete(np.arange(sample_lens[i]), frames)
+            mask[i, np.random.choice(free, want - len(frames), replace=False)] = True
+        mask[i, frames] = True
+    return mask
+
+
+def sample_negative_indices(y, num_neg):
+    """The draw of sample_negatives (wav2vec.py:318-326) as indices: (B,
+    T·num_neg) int64 on y's device, entry [b, t·num_neg + n] the row of
+    y.view(-1, C) that is negative n of frame (b, t).  Drawn from torch's CPU
+    generator exactly as the reference: randint(0, T-1), +1 where >= t, then
+    + b·(T-1).  That batch offset is the reference's — b·(T-1), not b·T — so
+    for b >= 1 the window is shifted b rows towards the previous utterance and
+    a frame can draw itself; the drop-in reproduces it."""
+    B, T, _ = y.shape
+    high = T - 1
+    with torch.no_grad():
+        targets = torch.arange(T).unsqueeze(-1).expand(-1, num_neg).flatten()
+        neg_indcs = torch.randint(low=0, high=high, size=(B, T * num_neg))
+        neg_indcs[neg_indcs >= targets] += 1
+        neg_indcs = neg_indcs + torch.arange(B).unsqueeze(1) * high
+    return neg_indcs.to(y.device)
+
+
+def sample_negatives(y, num_neg):
+    """wav2vec.py:305-330: (num_neg, B, T, C) negatives gathered from y
+    (differentiable).  ContrastiveLoss also takes sample_negative_indices(y,
+    num_neg) directly, which never builds this tensor."""
+    B, T, C = y.shape
+    idx = sample_negative_indices(y, num_neg)
+    negs = y.reshape(-1, C)[idx.view(-1)]
+    return negs.view(B, T, num_neg, C).permute(2, 0, 1, 3)
+
+
+def _pad_right(wavs):
+    """1-D waveforms → ((B, Smax) zero-padded, relative lengths (B,))."""
+    if len(wavs) == 1:
+        return wavs[0].unsqueeze(0), torch.tensor([1.0])
+    smax = max(w.shape[0] for w in wavs)
+    out = torch.stack([torch.nn.functional.pad(w, (0, smax - w.shape[0])) for w in wavs])
+    return out, torch.tensor([w.shape[0] / smax for w in wavs])
+
+
+def w2v_mask_collate_fn(samples_lst, get_out_len_fn, mask_prob, mask_length):
+    """wav2vec.py:333-382: samples ({"id", "sig"}) → (padded wavs (B, S),
+    relative lengths (B,), bool mask (B, T') over the extractor's frames)."""
+    wavs = [s["sig"] for s in samples_lst]
+    lens = [get_out_len_fn(torch.as_tensor(w.size(-1))).item() for w in wavs]
+    padded, wav_lens = _pad_right(wavs)
+    mask = compute_mask((len(wavs), max(lens)), lens, mask_prob, mask_length)
+    return torch.as_tensor(padded), torch.as_tensor(wav_lens), torch.as_tensor(mask, dtype=torch.bool)

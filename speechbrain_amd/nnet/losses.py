@@ -15,10 +15,16 @@ nll_loss / kldiv_loss: one HIP pass over the (B, U, V) log-probs gives each
 row's target log-prob t and row sum s; loss value and gradient follow from
 those two (B, U) tensors, so no (B, U, V) temporary (one-hot, smoothed
 distribution, transposed copy) is built.
+
+ContrastiveLoss (:1198-1251): one HIP kernel per row of x scores the positive
+and the negatives (cosine similarity, neg_is_pos, log-sum-exp, arg-max) with
+the candidate rows read in place; the sum over rows and the accuracy ratio are
+device-side torch (csrc/w2vloss.hip).
 """
 import math
 
 import torch
+import torch.nn as nn
 
 from .loss.ctc_loss import ctc_nll, row_stats
 from .loss.transducer_loss import TransducerLogits
@@ -156,3 +162,25 @@ def kldiv_loss(log_probabilities, targets, length=None, label_smoothing=0.0, all
             return loss.masked_fill(ignore.reshape(-1, 1), 0)
     else:
         return nll_loss(log_probabilities, targets, length, reduction=reduction)
+
+
+class ContrastiveLoss(nn.Module):
+    """losses.py:1198-1251.  forward(x, y, negs) → (loss, accuracy) for x, y
+    (B, T, C) and negs either
+      float (N, B, T, C)   the reference's call (sample_negatives): the kernel
+                           reads the candidate rows straight from negs;
+      integer (B, T·N)     lobes.models.wav2vec.sample_negative_indices: row
+                           indices into y.view(-1, C), negs is never built.
+    Both give the same values and gradients (wrt x, y and float negs).
+    Always computed in fp32, also under bf16 autocast: the reference's
+    `.type_as(x)` would round the cosine logits to x's dtype before the
+    cross-entropy; here they stay fp32 and the loss is returned in fp32."""
+
+    def __init__(self, logit_temp):
+        super().__init__()
+        self.logit_temp = logit_temp
+
+    def forward(self, x, y, negs):
+        from .. import _w2v
+        rowloss, correct, _ = _w2v.contrastive_rows(x, y, negs, self.logit_temp)
+        return rowloss.sum(), correct.detach().sum() / correct.numel()
