@@ -354,7 +354,7 @@ __global__ void __launch_bounds__(CM_NT) conv_module_kernel(ConvModArgs a) {
       }
       const float mu = t * a.inv_n;  // padded channels are zero: they add nothing to t or t2
       stat[row] = mu;
-      stat[CM_ROWS + row] = 1.0f / sqrtf(fmaxf(t2 * a.inv_n - mu * mu, 0.f) + a.eps0);
+      stat[CM_ROWS + row] = __builtin_amdgcn_rsqf(fmaxf(t2 * a.inv_n - mu * mu, 0.f) + a.eps0);
     }
     lds_barrier();
     const float4 g04 = *reinterpret_cast<const float4*>(gb0s + u0);
@@ -394,7 +394,7 @@ __global__ void __launch_bounds__(CM_NT) conv_module_kernel(ConvModArgs a) {
       float q = 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) q += (v[e] - mean) * (v[e] - mean);
-      const float rstd = 1.0f / sqrtf((wave_sum_v(q) - a.npad * mean * mean) * a.inv_n + a.eps0);
+      const float rstd = __builtin_amdgcn_rsqf((wave_sum_v(q) - a.npad * mean * mean) * a.inv_n + a.eps0);
       uint2 pk = make_uint2(0u, 0u);
       if (live) {
         pk.x = pack_bf16x2((v[0] - mean) * rstd * g04.x + b04.x, (v[1] - mean) * rstd * g04.y + b04.y);
@@ -582,7 +582,7 @@ __global__ void __launch_bounds__(CM_NT) conv_module_kernel(ConvModArgs a) {
     }
 #pragma unroll
     for (int u = 0; u < FPW; ++u)
-      rstd[u] = 1.0f / sqrtf((wave_sum_v(rstd[u]) - a.npad * mean[u] * mean[u]) * a.inv_n + a.eps1);
+      rstd[u] = __builtin_amdgcn_rsqf((wave_sum_v(rstd[u]) - a.npad * mean[u] * mean[u]) * a.inv_n + a.eps1);
 #pragma unroll
     for (int u = 0; u < FPW; ++u) {
 #pragma unroll

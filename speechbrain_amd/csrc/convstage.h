@@ -82,10 +82,21 @@ __device__ __forceinline__ int cs_gldu8(const uint8_t* p) {
   asm volatile("global_load_ubyte %0, %1, off" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
+// conv-stage marks of the chain's timeline buffer (probe builds only): 210 + i
+#define CS_TL(i) SBK_PROBE(if (blockIdx.x == 128 && lane == 0) g_ffn_tl[w][210 + (i)] = __builtin_amdgcn_s_memtime();)
 __device__ __forceinline__ void cs_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+}
+
+// 1 / (1 + exp(-x)) of a value pair, the sigmoid factor of GLU and Swish as
+// `rcpf(1.0f + __expf(-x))` computes it (v_exp_f32 of x * -log2(e), approx
+// rcp), with the multiply and the add in packed fp32
+__device__ __forceinline__ v2f cs_rcp1pexp(v2f x) {
+  const v2f t = x * v2f{-1.44269504088896340736f, -1.44269504088896340736f};
+  const v2f d = v2f{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + v2f{1.0f, 1.0f};
+  return v2f{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
 // One tile (frames t0 .. t0 + 47 of utterance b) of the convolution module on
@@ -107,6 +118,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
   const int f0 = t0 - a.padL;  // frame of staged row 0
   const int nrows = CS_BM + a.K - 1;
   const long long ubase = (long long)b * a.T;
+  CS_TL(0);
 
   // ---- phase -1: x_att = x + o wo^T + bo over the staged frames, LN0 -> U
   float4 xres[2][CS_MT3];
@@ -155,6 +167,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     if (tid < CS_D / 2) *reinterpret_cast<float4*>(gb0s + 4 * tid) = gbv;
     stage();
     cs_barrier();
+    CS_TL(1);
     f32x4 acc[2][CS_MT1];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -173,18 +186,22 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) {
-        xa[j][mt][0] = xv[j][mt].x + (acc[j][mt][0] + bo4[j].x);
-        xa[j][mt][1] = xv[j][mt].y + (acc[j][mt][1] + bo4[j].y);
-        xa[j][mt][2] = xv[j][mt].z + (acc[j][mt][2] + bo4[j].z);
-        xa[j][mt][3] = xv[j][mt].w + (acc[j][mt][3] + bo4[j].w);
+        const v2f lo = v2f{xv[j][mt].x, xv[j][mt].y} + (v2f{acc[j][mt][0], acc[j][mt][1]} + v2f{bo4[j].x, bo4[j].y});
+        const v2f hi = v2f{xv[j][mt].z, xv[j][mt].w} + (v2f{acc[j][mt][2], acc[j][mt][3]} + v2f{bo4[j].z, bo4[j].w});
+        xa[j][mt][0] = lo[0];
+        xa[j][mt][1] = lo[1];
+        xa[j][mt][2] = hi[0];
+        xa[j][mt][3] = hi[1];
       }
     // phase 3's residual: output frame mt*16 + fr is staged row mt*16 + fr +
     // padL, held (same units) by lane (fr + padL) % 16 of tile (mt*16 + fr +
-    // padL) / 16: two lane permutes per value and a select
+    // padL) / 16.  The lane map is a permutation, so the source lane knows
+    // its reader: lane fr is read for the upper tile exactly when fr < rr
+    // (reader fr - rr + 16), and selects before the one permute per value
     {
       const int q = a.padL >> 4, rr = a.padL & 15;  // q <= 1 (K <= 31)
       const int src = ((lane & 0x30) + ((fr + rr) & 15)) << 2;
-      const bool hi = fr + rr >= 16;
+      const bool hi = fr < rr;
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -194,9 +211,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
           for (int e = 0; e < 4; ++e) {
             const float lo_v = q == 0 ? xa[j][mt][e] : xa[j][mt + 1][e];
             const float hi_v = q == 0 ? xa[j][mt + 1][e] : xa[j][mt + 2][e];
-            const float lo = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(lo_v)));
-            const float hv = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(hi_v)));
-            v[e] = hi ? hv : lo;
+            v[e] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(hi ? hi_v : lo_v)));
           }
           xres[j][mt] = make_float4(v[0], v[1], v[2], v[3]);
         }
@@ -207,19 +222,22 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     float* red = lnscr;  // [CS_ROWS][RS] sums, then [CS_ROWS][RS] squares
 #pragma unroll
     for (int mt = 0; mt < CS_MT1; ++mt) {
-      float s = 0.f, q2 = 0.f;
+      v2f s2 = v2f{0.f, 0.f}, q2 = v2f{0.f, 0.f};  // value pairs (e, e + 1): packed adds / fmas
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        s += (xa[j][mt][0] + xa[j][mt][1]) + (xa[j][mt][2] + xa[j][mt][3]);
-        q2 += (xa[j][mt][0] * xa[j][mt][0] + xa[j][mt][1] * xa[j][mt][1]) +
-              (xa[j][mt][2] * xa[j][mt][2] + xa[j][mt][3] * xa[j][mt][3]);
-      }
-      const float ps = col4_sum(s), pq = col4_sum(q2);
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+          const v2f xx = v2f{xa[j][mt][e], xa[j][mt][e + 1]};
+          s2 += xx;
+          q2 = __builtin_elementwise_fma(xx, xx, q2);
+        }
+      const float ps = col4_sum(s2[0] + s2[1]), pq = col4_sum(q2[0] + q2[1]);
       if (g == 0) {
         red[(mt * 16 + fr) * RS + w] = ps;
         red[CS_ROWS * RS + (mt * 16 + fr) * RS + w] = pq;
       }
     }
+    CS_TL(2);
     cs_barrier();
     // every wave is past its reads of Gs: phase 1's first two tiles land
     // under the statistics exchange and the LN0 application
@@ -238,7 +256,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
       }
       const float mu = t * inv_n;  // padded channels are zero: they add nothing to t or t2
       stat[row] = mu;
-      stat[CS_ROWS + row] = 1.0f / sqrtf(fmaxf(t2 * inv_n - mu * mu, 0.f) + a.eps0);
+      stat[CS_ROWS + row] = __builtin_amdgcn_rsqf(fmaxf(t2 * inv_n - mu * mu, 0.f) + a.eps0);  // v_rsq_f32, 1 ulp
     }
     cs_barrier();
 #pragma unroll
@@ -253,14 +271,18 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
         const bool live = r < nrows && f >= 0 && f < a.T;
         uint2 pk = make_uint2(0u, 0u);
         if (live) {
-          pk.x = pack_bf16x2((xa[j][mt][0] - mean) * rstd * g04.x + b04.x, (xa[j][mt][1] - mean) * rstd * g04.y + b04.y);
-          pk.y = pack_bf16x2((xa[j][mt][2] - mean) * rstd * g04.z + b04.z, (xa[j][mt][3] - mean) * rstd * g04.w + b04.w);
+          const v2f m2 = v2f{mean, mean}, r2 = v2f{rstd, rstd};
+          const v2f lo = (v2f{xa[j][mt][0], xa[j][mt][1]} - m2) * r2 * v2f{g04.x, g04.y} + v2f{b04.x, b04.y};
+          const v2f hi = (v2f{xa[j][mt][2], xa[j][mt][3]} - m2) * r2 * v2f{g04.z, g04.w} + v2f{b04.z, b04.w};
+          pk.x = pack_bf16x2(lo[0], lo[1]);
+          pk.y = pack_bf16x2(hi[0], hi[1]);
         }
         *reinterpret_cast<uint2*>(Us + r * CS_S + (u0 ^ ffn_sw(fr))) = pk;
       }
     }
   }
   cs_barrier();
+  CS_TL(3);
 
   // ---- phase 1: G = GLU(U W1p^T + b1p) over CS_ROWS frames.  Tile q = K-step
   // q / 2, half q % 2: wave w's rows of it are GLU group 2w + q % 2 (16 value
@@ -304,6 +326,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
           for (int mt = 0; mt < CS_MT1; ++mt) acc[h][t][mt] = FFN_MFMA(fw[ks][t], fa[ks][mt], acc[h][t][mt]);
     }
     cs_barrier();  // every wave's ring reads are done before G overwrites Gs
+    CS_TL(4);
     // GLU epilogue: lane holds frames mt*16 + fr, units 4g..4g+3 of each
     // tile; tiles (0, 1) = (value, gate) of channel group 2w + h
 #pragma unroll
@@ -312,26 +335,27 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
       const int pa = (w * 2 + h) * 32 + 4 * g, pg = pa + 16;  // permuted rows of value / gate
       const float4 ba = *reinterpret_cast<const float4*>(a.b1 + pa);
       const float4 bg = *reinterpret_cast<const float4*>(a.b1 + pg);
-      const float bav[4] = {ba.x, ba.y, ba.z, ba.w}, bgv[4] = {bg.x, bg.y, bg.z, bg.w};
+      const v2f bav[2] = {v2f{ba.x, ba.y}, v2f{ba.z, ba.w}}, bgv[2] = {v2f{bg.x, bg.y}, v2f{bg.z, bg.w}};
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) {
         const int r = mt * 16 + fr, f = f0 + r;
         const bool live = r < nrows && f >= 0 && f < a.T;
-        float o[4];
+        // value pairs (e, e + 1) in packed fp32; dead frames masked on the packed bf16 words
+        uint32_t o[2];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float va = acc[h][0][mt][e] + bav[e], vg = acc[h][1][mt][e] + bgv[e];
-          const float sg = va * __builtin_amdgcn_rcpf(1.0f + __expf(-vg));  // bf16 output: approx rcp
-          o[e] = live ? sg : 0.f;
+        for (int e2 = 0; e2 < 2; ++e2) {
+          const v2f va = v2f{acc[h][0][mt][2 * e2], acc[h][0][mt][2 * e2 + 1]} + bav[e2];
+          const v2f vg = v2f{acc[h][1][mt][2 * e2], acc[h][1][mt][2 * e2 + 1]} + bgv[e2];
+          const v2f sg = va * cs_rcp1pexp(vg);  // bf16 output: approx rcp
+          o[e2] = pack_bf16x2(sg[0], sg[1]);
         }
-        uint2 pk;
-        pk.x = pack_bf16x2(o[0], o[1]);
-        pk.y = pack_bf16x2(o[2], o[3]);
+        const uint2 pk = live ? make_uint2(o[0], o[1]) : make_uint2(0u, 0u);
         *reinterpret_cast<uint2*>(Gs + r * CS_S + (ch ^ ffn_sw(fr))) = pk;
       }
     }
   }
   cs_barrier();
+  CS_TL(5);
 
   // ---- phase 2a: depthwise conv, thread (channel c, half h) over 24 frames,
   // two taps per v_dot2 (bf16 operands, fp32 accumulation) -> fp32 tile
@@ -377,6 +401,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     }
   }
   cs_barrier();
+  CS_TL(6);
 
   // ---- phase 2b: LN1 -> Swish -> V (over U), one wave per frame, 4 channels
   // per lane.  Gs is free: phase 3's first tile lands under this phase (the
@@ -405,40 +430,42 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     for (int mt = 0; mt < CS_MT3; ++mt) asm volatile("" : "+v"(km[mt]));
     if (!a.b2) bb2[0] = bb2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (!a.kpm) km[0] = km[1] = km[2] = 0;
-    const float gm[4] = {g14[0], g14[1], g14[2], g14[3]}, bt[4] = {b14[0], b14[1], b14[2], b14[3]};
+    const v2f gm[2] = {v2f{g14[0], g14[1]}, v2f{g14[2], g14[3]}}, bt[2] = {v2f{b14[0], b14[1]}, v2f{b14[2], b14[3]}};
     constexpr int FPW = CS_BM / CS_NW;  // frames per wave, side by side: their reduction chains interleave
-    float v[FPW][4], mean[FPW], rstd[FPW];
+    // channel pairs (e, e + 1) in packed fp32 (two-pass variance, as before)
+    v2f v[FPW][2];
+    float mean[FPW], rstd[FPW];
 #pragma unroll
     for (int u = 0; u < FPW; ++u) {
       const float4 v4 = *reinterpret_cast<const float4*>(Cv + (w + u * CS_NW) * CS_D + lane * 4);
-      v[u][0] = v4.x; v[u][1] = v4.y; v[u][2] = v4.z; v[u][3] = v4.w;
+      v[u][0] = v2f{v4.x, v4.y};
+      v[u][1] = v2f{v4.z, v4.w};
     }
 #pragma unroll
-    for (int u = 0; u < FPW; ++u) mean[u] = wave_sum_v((v[u][0] + v[u][1]) + (v[u][2] + v[u][3])) * inv_n;
+    for (int u = 0; u < FPW; ++u) mean[u] = wave_sum_v((v[u][0][0] + v[u][0][1]) + (v[u][1][0] + v[u][1][1])) * inv_n;
 #pragma unroll
     for (int u = 0; u < FPW; ++u) {
-      float q = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) q += (v[u][e] - mean[u]) * (v[u][e] - mean[u]);
-      rstd[u] = q;
+      const v2f m2 = v2f{mean[u], mean[u]}, d0 = v[u][0] - m2, d1 = v[u][1] - m2;
+      const v2f q = __builtin_elementwise_fma(d1, d1, d0 * d0);
+      rstd[u] = q[0] + q[1];
     }
 #pragma unroll
-    for (int u = 0; u < FPW; ++u)
-      rstd[u] = 1.0f / sqrtf((wave_sum_v(rstd[u]) - npad * mean[u] * mean[u]) * inv_n + a.eps1);
+    for (int u = 0; u < FPW; ++u)  // v_rsq_f32 (1 ulp) on a value >= eps
+      rstd[u] = __builtin_amdgcn_rsqf((wave_sum_v(rstd[u]) - npad * mean[u] * mean[u]) * inv_n + a.eps1);
 #pragma unroll
     for (int u = 0; u < FPW; ++u) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float z = (v[u][e] - mean[u]) * rstd[u] * gm[e] + bt[e];
-        v[u][e] = z * __builtin_amdgcn_rcpf(1.0f + __expf(-z));  // bf16 output (as the GLU above)
-      }
       uint2 pk;
-      pk.x = pack_bf16x2(v[u][0], v[u][1]);
-      pk.y = pack_bf16x2(v[u][2], v[u][3]);
+#pragma unroll
+      for (int e2 = 0; e2 < 2; ++e2) {
+        const v2f z = (v[u][e2] - v2f{mean[u], mean[u]}) * v2f{rstd[u], rstd[u]} * gm[e2] + bt[e2];
+        const v2f sw = z * cs_rcp1pexp(z);  // bf16 output (as the GLU above)
+        (e2 ? pk.y : pk.x) = pack_bf16x2(sw[0], sw[1]);
+      }
       *reinterpret_cast<uint2*>(Us + (w + u * CS_NW) * CS_S + ((lane * 4) ^ ffn_sw(w))) = pk;  // CS_NW % 8 == 0
     }
   }
   cs_barrier();
+  CS_TL(7);
 
   // ---- phase 3: z = x_att + rowmask0(V W2^T + b2), kept in registers
   {
@@ -479,12 +506,12 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
         const bool live = t0 + mt * 16 + fr < a.T;
         const bool m = km[mt] != 0;
         const float4 xv = xres[j][mt];
-        f32x4 o;
-        o[0] = xv.x + (m ? 0.f : acc[j][mt][0] + bb2[j][0]);
-        o[1] = xv.y + (m ? 0.f : acc[j][mt][1] + bb2[j][1]);
-        o[2] = xv.z + (m ? 0.f : acc[j][mt][2] + bb2[j][2]);
-        o[3] = xv.w + (m ? 0.f : acc[j][mt][3] + bb2[j][3]);
-        zres[j][mt] = live ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+        const v2f z2 = v2f{0.f, 0.f};
+        const v2f c0 = v2f{acc[j][mt][0], acc[j][mt][1]} + v2f{bb2[j][0], bb2[j][1]};
+        const v2f c1 = v2f{acc[j][mt][2], acc[j][mt][3]} + v2f{bb2[j][2], bb2[j][3]};
+        const v2f o0 = v2f{xv.x, xv.y} + (m ? z2 : c0), o1 = v2f{xv.z, xv.w} + (m ? z2 : c1);
+        zres[j][mt] = live ? f32x4{o0[0], o0[1], o1[0], o1[1]} : f32x4{0.f, 0.f, 0.f, 0.f};
       }
   }
+  CS_TL(8);
 }

@@ -80,6 +80,13 @@
 // Ws streamed through the ring from its own image, the accumulators the
 // residual layout; it also stores its rows' key-padding bytes (37.6 us
 // against 32.9 + ~12 + 5.0).
+// Round 9: the phases that are not GEMM run with the MFMA pipe and the weight
+// stream idle on every CU at once, so their VALU issue is on the critical
+// path.  row_ln, the epilogues and the conv stage take v_rsq_f32 instead of
+// the IEEE 1 / sqrt expansion and packed fp32 pairs (v2f) where the values
+// sit in adjacent registers; the rounding points are where they were.
+// conv_chain_kernel<1>: 4,444 -> 3,721 static VALU instructions per wave,
+// 161.7k -> 155.4k cycles, 76.3 -> 73.6 us.
 #include "mfma.h"
 
 using namespace sbk;
@@ -158,6 +165,8 @@ static_assert(FFN_NW % 8 == 0, "rows w + FFN_NW * i share bit 2 with w (their sw
 // stores (16 lanes, rows fr) are 2-way and whose b128 reads are conflict-free
 // (a stride of NW = 8 made them 4-way and 2-way: 66 conflict cycles per LayerNorm)
 constexpr int FFN_RS = 12;
+
+typedef float v2f __attribute__((ext_vector_type(2)));  // fp32 pairs: v_pk_add / v_pk_mul / v_pk_fma
 
 #define FFN_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
 
@@ -252,6 +261,7 @@ __device__ __forceinline__ void row_ln(float (&z)[T2][MT][4], float* red, const 
     float part[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
+      // (packed pair sums here cost the GELU chain instance 4 more bytes of scratch)
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < T2; ++j)
@@ -280,8 +290,8 @@ __device__ __forceinline__ void row_ln(float (&z)[T2][MT][4], float* red, const 
       tie(rv[mt][1]);
       const float t = (rv[mt][0][0] + rv[mt][0][1]) + (rv[mt][0][2] + rv[mt][0][3]) + (rv[mt][1][0] + rv[mt][1][1]) +
                       (rv[mt][1][2] + rv[mt][1][3]);
-      if (pass)
-        rstd[mt] = 1.0f / sqrtf((t - npad * mean[mt] * mean[mt]) * inv_n + eps);
+      if (pass)  // v_rsq_f32 (1 ulp) on a value >= eps, instead of the IEEE sqrt and divide expansions
+        rstd[mt] = __builtin_amdgcn_rsqf((t - npad * mean[mt] * mean[mt]) * inv_n + eps);
       else
         mean[mt] = t * inv_n;
     }
@@ -298,9 +308,14 @@ __device__ __forceinline__ void row_ln(float (&z)[T2][MT][4], float* red, const 
     tie(gv[j]);
     tie(bv[j]);
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
+    for (int e = 0; e < 4; e += 2)
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) z[j][mt][e] = (z[j][mt][e] - mean[mt]) * rstd[mt] * gv[j][e] + bv[j][e];
+      for (int mt = 0; mt < MT; ++mt) {
+        const v2f y = (v2f{z[j][mt][e], z[j][mt][e + 1]} - v2f{mean[mt], mean[mt]}) * v2f{rstd[mt], rstd[mt]} *
+                          v2f{gv[j][e], gv[j][e + 1]} + v2f{bv[j][e], bv[j][e + 1]};
+        z[j][mt][e] = y[0];
+        z[j][mt][e + 1] = y[1];
+      }
   }
 }
 
@@ -326,11 +341,12 @@ __device__ __forceinline__ void load_frags(bf16x8 (&xa)[K1][KS][MT], const bf16_
       for (int mt = 0; mt < MT; ++mt) tie(xa[r][ks][mt]);
 }
 
-#include "convstage.h"
-
-// s_memtime timeline of the waves of workgroup 128 (probe builds only)
+// s_memtime timeline of the waves of workgroup 128 (probe builds only; the
+// conv stage's marks are entries 210.. of each wave's row)
 SBK_PROBE_BUFFER(g_ffn_tl, 16, 256)
 #define FFN_TL(i) SBK_PROBE(if (tl_rec >= 0 && lane == 0) g_ffn_tl[tl_rec][i] = __builtin_amdgcn_s_memtime();)
+
+#include "convstage.h"
 
 // The body of ffn_kernel and conv_chain_kernel.  CONV: the workgroup's rows
 // are one 48-frame tile of one utterance and come out of the convolution
@@ -604,7 +620,7 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
     float q = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) q += (v[e] - mean) * (v[e] - mean);
-    const float rstd = 1.0f / sqrtf((wave_sum_v(q) - a.npad * mean * mean) * a.inv_n + a.eps0);
+    const float rstd = __builtin_amdgcn_rsqf((wave_sum_v(q) - a.npad * mean * mean) * a.inv_n + a.eps0);
     uint2 pk;
     pk.x = pack_bf16x2((v[0] - mean) * rstd * g04[0] + b04[0], (v[1] - mean) * rstd * g04[1] + b04[1]);
     pk.y = pack_bf16x2((v[2] - mean) * rstd * g04[2] + b04[2], (v[3] - mean) * rstd * g04[3] + b04[3]);
@@ -724,10 +740,13 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const f32x4 xr = xres[j][mt];
-        z[j][mt][0] = xr[0] + a.alpha * (acc2[j][mt][0] + bb[0]);
-        z[j][mt][1] = xr[1] + a.alpha * (acc2[j][mt][1] + bb[1]);
-        z[j][mt][2] = xr[2] + a.alpha * (acc2[j][mt][2] + bb[2]);
-        z[j][mt][3] = xr[3] + a.alpha * (acc2[j][mt][3] + bb[3]);
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+          const v2f zz = v2f{xr[e], xr[e + 1]} +
+                         v2f{a.alpha, a.alpha} * (v2f{acc2[j][mt][e], acc2[j][mt][e + 1]} + v2f{bb[e], bb[e + 1]});
+          z[j][mt][e] = zz[0];
+          z[j][mt][e + 1] = zz[1];
+        }
         acc1[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc2[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -788,10 +807,13 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const f32x4 xr = xres[j][mt];
-      z[j][mt][0] = xr[0] + alphaf * (acc2[j][mt][0] + bb[0]);
-      z[j][mt][1] = xr[1] + alphaf * (acc2[j][mt][1] + bb[1]);
-      z[j][mt][2] = xr[2] + alphaf * (acc2[j][mt][2] + bb[2]);
-      z[j][mt][3] = xr[3] + alphaf * (acc2[j][mt][3] + bb[3]);
+#pragma unroll
+      for (int e = 0; e < 4; e += 2) {
+        const v2f zz = v2f{xr[e], xr[e + 1]} +
+                       v2f{alphaf, alphaf} * (v2f{acc2[j][mt][e], acc2[j][mt][e + 1]} + v2f{bb[e], bb[e + 1]});
+        z[j][mt][e] = zz[0];
+        z[j][mt][e + 1] = zz[1];
+      }
     }
   }
   FFN_TL(195);
