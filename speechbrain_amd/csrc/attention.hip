@@ -170,9 +170,15 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float q = my_i < Tn ? qf[e] : 0.f;
-        qu[e] = my_i < Tn ? (q + pbu[h * dh + d0 + e]) * qscale : 0.f;
-        qv[e] = my_i < Tn ? (q + pbv[h * dh + d0 + e]) * qscale : 0.f;
+        // fp32 with dh % 8 == 4: the fragment's upper half lies past this
+        // head's dims (qf holds the K section's first values there, and the
+        // biases would be the next head's, or past the end of the vectors for
+        // the last head).  Bias loads stay unconditional on a clamped index;
+        // those dims are zero in the fragment.
+        const bool live = my_i < Tn && d0 + e < dh;
+        const int db = h * dh + min(d0 + e, dh - 1);
+        qu[e] = live ? (qf[e] + pbu[db]) * qscale : 0.f;
+        qv[e] = live ? (qf[e] + pbv[db]) * qscale : 0.f;
       }
     } else {
 #pragma unroll
@@ -941,7 +947,8 @@ SBK_API int sbk_relpos_attention_mask(int dtype_bf16, const void* qkv, const voi
                                       const float* pbv, const uint8_t* kpm, const float* am, long long am_sb,
                                       long long am_sh, int B, int Tn, int H, int dh, float scale, void* out,
                                       float* probs, void* stream) {
-  if (B <= 0 || Tn <= 0 || H <= 0 || dh <= 0 || dh > 128 || ldp < H * dh || !am || am_sb < 0 || am_sh < 0)
+  if (B <= 0 || Tn <= 0 || H <= 0 || dh <= 0 || dh > 128 || ldp < H * dh || !pk || !am || am_sb < 0 ||
+      am_sh < 0)
     return SBK_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (dtype_bf16)

@@ -45,6 +45,13 @@ def test_library_exports_header_symbols():
                                       ctypes.c_void_p, ctypes.c_void_p]
     assert lib.sbk_layernorm_wide(None, 4, 16385, None, None, 1e-5, None, 0, None) == 1001
     assert lib.sbk_layernorm_bwd(None, None, 0, 4, 16385, None, 1e-5, None, None, None, None) == 1001
+    # masked rel-pos attention: a null positional table is refused before any
+    # launch, as sbk_relpos_attention_ld refuses it (valid shapes, non-null mask)
+    from speechbrain_amd import _lib as L
+    lib.sbk_relpos_attention_mask.argtypes = L.SIGNATURES["sbk_relpos_attention_mask"]
+    am = (ctypes.c_float * 4)()
+    assert lib.sbk_relpos_attention_mask(0, None, None, 64, None, None, None, ctypes.cast(am, ctypes.c_void_p), 0, 0,
+                                         1, 2, 1, 64, 0.125, None, None, None) == 1001
 
 
 def test_no_cpu_fallback():
