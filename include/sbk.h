@@ -880,6 +880,49 @@ int sbk_gumbel_vq_bwd(const float* dout, const float* vars, const float* logits,
                       const float* gpsum, float tau, const long long* order, const long long* offs, int Rq, int G,
                       int V, int ncodes, int D, float* dlogits, float* dvars, void* stream);
 
+/* ---- gru.hip: GRU recurrence (nnet/RNN.py:280-388) and Embedding (nnet/embedding.py) ---- */
+
+/* The T forward steps of one GRU layer, one launch per step (torch.nn.GRU
+ * semantics, gate order r, z, n).  bf16 != 0: w_hh (3H, H) is bf16 and the
+ * h_{t-1} operand is rounded to bf16; else fp32 and exact-fp32 MFMA.  The
+ * state is fp32 in both.  Input pre-activations: gi (B, T, 3H) fp32 with b_ih
+ * already added, or tok (B, T) int32 token ids with table = W_ih^T (I, 3H)
+ * fp32 and b_ih (3H) or null — token `blank` adds b_ih only, ids above it
+ * read row id - 1.  Exactly one of gi / tok.  b_hh (3H) or null; hx (B, H)
+ * or null (zeros); lens (B) int32 = steps per row, or null: a row keeps its
+ * state from step lens[b] on and its y rows are zero there.  state (B, T, H)
+ * = the carried state after every step; y (B, T, H) or null; save
+ * (B, T, 4, H) or null = r, z, n and W_hn h + b_hn for the backward.  Any
+ * B, T, H, I >= 1.  A null required pointer, a size <= 0, both or neither of
+ * gi / tok: 1001. */
+int sbk_gru_fwd(int bf16, const void* w_hh, const float* b_hh, const float* hx, const float* gi, const int* tok,
+                int blank, const float* table, int I, const float* b_ih, const int* lens, int B, int T, int H,
+                float* state, float* y, float* save, void* stream);
+
+/* The backward steps t = T-1 .. 0 and the carry into dhx, one launch each.
+ * w_hhT = W_hh^T (H, 3H) in the compute dtype; hx, state, save, lens as given
+ * to / written by sbk_gru_fwd; dy (B, T, H) or null; dhn (B, H) or null.
+ * Writes dgi and dgh = (dr, dz, dn * r) (B, T, 3H) fp32, zero past a row's
+ * length, and dhx (B, H).  dhw (2, B, H) fp32 is scratch.  No atomics. */
+int sbk_gru_bwd(int bf16, const void* w_hhT, const float* hx, const float* state, const float* save, const float* dy,
+                const float* dhn, const int* lens, int B, int T, int H, float* dgi, float* dgh, float* dhw,
+                float* dhx, void* stream);
+
+/* out (N, V-1) fp32: the one-hot rows of ids (N) int32 as Embedding(
+ * consider_as_one_hot=True) returns them: a zero row for `blank`, ids above
+ * it shifted down by one.  V <= 1 or blank outside [0, V): 1001. */
+int sbk_embed_onehot(const int* ids, int N, int V, int blank, float* out, void* stream);
+
+/* out (N, D) fp32 = weight (V, D)[ids (N) int32]; an id outside [0, V) gives a zero row. */
+int sbk_embed_gather(const int* ids, const float* weight, int N, int V, int D, float* out, void* stream);
+
+/* out (ncodes, D) fp32 = per-code sums of the rows of src (items, D) fp32.
+ * order (items) int64 = row ids sorted stably by code, offs (ncodes+1) int64
+ * = the start of every code's run.  Added in list order: no atomics, bitwise
+ * reproducible (the Embedding weight gradient; dW_ih of a one-hot GRU input). */
+int sbk_segsum_rows(const float* src, const long long* order, const long long* offs, long long items, int ncodes,
+                    int D, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

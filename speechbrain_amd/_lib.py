@@ -142,8 +142,14 @@ SIGNATURES = {
     "sbk_gumbel_vq_parts": [_i, _i],
     "sbk_gumbel_vq_fwd": [_vp, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "sbk_gumbel_vq_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    # gru.hip (GRU recurrence, one launch per step; Embedding gather / one-hot / segment sum)
+    "sbk_gru_fwd": [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "sbk_gru_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "sbk_embed_onehot": [_vp, _i, _i, _i, _vp, _vp],
+    "sbk_embed_gather": [_vp, _vp, _i, _i, _i, _vp, _vp],
+    "sbk_segsum_rows": [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp],
     # attention.hip
-    "sbk_relpos_attention": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
+    "sbk_relpos_attention":[_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],
     "sbk_relpos_attention_mask": [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _ll, _ll, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_ld": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
