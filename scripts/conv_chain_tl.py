@@ -1,6 +1,8 @@
 """s_memtime timeline of the fused layer kernel (sbk_conv_ffn_chain: conv
 module of layer i, FFN2 + norm2 of layer i, FFN1 + norm1 + in_proj of layer
-i+1) for every wave of workgroup 128, at the headline shape (B = 32, T = 376,
+i+1) for every wave of workgroup 128 (a full tile) and of workgroup 127 (the
+last tile of an utterance, 40 live rows: the projection tail stores at the
+block ends and after the loop), at the headline shape (B = 32, T = 376,
 H = 1024, kernel size 31).  Probe build with -DSBK_PROBE_TL; never the product.
 usage: scripts/probe_build.sh speechbrain_amd/csrc/ffn.hip TL, then
        SBK_PROBE_LIB=<the TL probe library it wrote> python scripts/conv_chain_tl.py"""
@@ -40,7 +42,6 @@ buf = (ctypes.c_ulonglong * (16 * 256))()
 lib = ctypes.CDLL(_L.LIB_PATH)
 assert lib.sbk_probe_ffn_tl(buf) == 0
 tl = np.array(buf, dtype=np.int64).reshape(16, 256)
-rel = tl[:8] - tl[:8, 0].min()
 # marks in program order: conv stage 210 .. 218, chain 1, A steps, 197 .. 198, B steps, 194 .. 196
 names = [("start", 0), ("cs in", 210), ("staged", 211), ("out_proj+sums", 212), ("LN0", 213), ("ph1 gemm", 214),
          ("GLU", 215), ("ph2a", 216), ("ph2b", 217), ("ph3", 218), ("A LN0 (loop)", 1), ("A steps", 3 + 2 * 31),
@@ -48,16 +49,22 @@ names = [("start", 0), ("cs in", 210), ("staged", 211), ("out_proj+sums", 212), 
          ("B steps", 3 + 2 * 63), ("epi in", 194), ("epi z", 195), ("nextLN", 204), ("Zo/Xn bar", 205),
          ("proj", 206), ("end", 196)]
 print("s_memtime ticks (as the committed chain timelines), wave by wave; each column: mark time / delta to the previous")
-for w in range(8):
-    r = rel[w]
-    prev, cells = r[0], []
+for wg, rows in ((128, tl[:8]), (127, tl[8:])):
+    # each workgroup against its own first mark (the two run on different XCDs)
+    rel = rows - rows[:, 0].min()
+    print(f"workgroup {wg} ({'full tile' if wg == 128 else 'last tile of utterance 15, 40 live rows'}):")
+    for w in range(8):
+        r = rel[w]
+        prev, cells = r[0], []
+        for nm, i in names:
+            cells.append(f"{nm} {r[i]}/{r[i] - prev}")
+            prev = r[i]
+        print(f"w{w}: " + " | ".join(cells))
+    med = np.median(rel, axis=0).astype(np.int64)
+    prev = med[0]
+    print(f"median over the waves of workgroup {wg}:")
     for nm, i in names:
-        cells.append(f"{nm} {r[i]}/{r[i] - prev}")
-        prev = r[i]
-    print(f"w{w}: " + " | ".join(cells))
-med = np.median(rel, axis=0).astype(np.int64)
-prev = med[0]
-print("median over the waves:")
-for nm, i in names:
-    print(f"  {nm:16s} at {med[i]:7d}  +{med[i] - prev}")
-    prev = med[i]
+        print(f"  {nm:16s} at {med[i]:7d}  +{med[i] - prev}")
+        prev = med[i]
+    print(f"  end of the last wave {rel[:, 196].max()}, waves 0-3 proj {np.median(rel[:4, 206] - rel[:4, 205]):.0f}, "
+          f"waves 4-7 proj {np.median(rel[4:, 206] - rel[4:, 205]):.0f}")

@@ -83,7 +83,9 @@ __device__ __forceinline__ int cs_gldu8(const uint8_t* p) {
   return v;
 }
 // conv-stage marks of the chain's timeline buffer (probe builds only): 210 + i
-#define CS_TL(i) SBK_PROBE(if (blockIdx.x == 128 && lane == 0) g_ffn_tl[w][210 + (i)] = __builtin_amdgcn_s_memtime();)
+#define CS_TL(i)                                                                    \
+  SBK_PROBE(if ((blockIdx.x == 128 || blockIdx.x == 127) && lane == 0)              \
+                g_ffn_tl[(blockIdx.x == 127 ? 8 : 0) + w][210 + (i)] = __builtin_amdgcn_s_memtime();)
 __device__ __forceinline__ void cs_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();

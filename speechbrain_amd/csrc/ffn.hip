@@ -24,8 +24,9 @@
 //     phase 2: acc2^T += W2[:, c]·Hs^T  (accumulators stay in VGPRs);
 //   epilogue : +b2, alpha, residual, optional post-LN and next-LN over the
 //              full rows (cross-wave reduction through LDS), float4 stores;
-//   tail     : (projection) u -> Xn -> VGPR fragments, K1 steps per 256
-//              output columns of Wp through the same ring, bf16 stores.
+//   tail     : (projection) u -> Xn (LDS), its fragments read in each of the
+//              K1 steps per 256 output columns of Wp through the same ring;
+//              bf16 stores of 16 B, interleaved into the next block's steps.
 // Weight tiles (256 rows x 64 k = 32 KB) stream L2 -> LDS by LDS-DMA
 // (global_load_lds_dwordx4: full 128-B lines, no VGPRs) into a 2-slot ring,
 // one tile in flight behind the one being read (counted vmcnt; the last FFN
@@ -87,6 +88,17 @@
 // sit in adjacent registers; the rounding points are where they were.
 // conv_chain_kernel<1>: 4,444 -> 3,721 static VALU instructions per wave,
 // 161.7k -> 155.4k cycles, 76.3 -> 73.6 us.
+// Round 10: the projection tail (the in_proj of the next layer, 11 % of the
+// chain launch).  Its y rows went out as two 8-B stores per lane and row
+// (units 4g.. of the wave's two 16-column tiles, 32 B apart): 18 store
+// instructions per wave and column block, and the waves that finish last
+// queued behind their issue.  One v_permlane16_swap pair per row exchanges
+// tiles between lane rows, so a lane holds 8 consecutive columns and stores
+// 16 B: 9 instructions, same bytes, same values.  Timeline of workgroup 128:
+// tail 17.5k -> 14.0k cycles, launch 157.6k -> 152.7k; conv_chain_kernel<1>
+// 73.9 -> 72.4 us.  Holding u's fragments in VGPRs for the 12 steps (as phase
+// 1 does) was measured on top and alone: no gain either way (DESIGN section
+// 3, round 10).
 #include "mfma.h"
 
 using namespace sbk;
@@ -319,6 +331,21 @@ __device__ __forceinline__ void row_ln(float (&z)[T2][MT][4], float* red, const 
   }
 }
 
+// The projection's bf16 results of one row, paired for a 16-B store.  A lane
+// (g, fr) holds units 4g .. 4g+3 of the wave's tile 0 (v0) and of tile 1 (v1),
+// 32 B apart.  v_permlane16_swap exchanges tile 1 of the even lane rows
+// (g = 0, 2) with tile 0 of the odd ones, row fr by row fr: afterwards the
+// lane holds units 8 (g >> 1) .. +7 of tile g & 1, i.e. the 8 consecutive
+// columns 16 (g & 1) + 8 (g >> 1) .. of the wave's 32.  (The same pairing by
+// a row permutation of the image's projection tiles would change the image.)
+__device__ __forceinline__ uint4 proj_pair(const f32x4& v0, const f32x4& v1) {
+  const uint32_t a0 = pack_bf16x2(v0[0], v0[1]), a1 = pack_bf16x2(v0[2], v0[3]);
+  const uint32_t b0 = pack_bf16x2(v1[0], v1[1]), b1 = pack_bf16x2(v1[2], v1[3]);
+  const auto lo = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
+  const auto hi = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+  return make_uint4(lo[0], hi[0], lo[1], hi[1]);
+}
+
 // A-operand fragments of the LayerNorm'd rows (Xn, bf16, row stride XS)
 // into VGPRs for every K-step of a block
 template <int K1, int KS, int MT, int XS, int BK>
@@ -341,8 +368,10 @@ __device__ __forceinline__ void load_frags(bf16x8 (&xa)[K1][KS][MT], const bf16_
       for (int mt = 0; mt < MT; ++mt) tie(xa[r][ks][mt]);
 }
 
-// s_memtime timeline of the waves of workgroup 128 (probe builds only; the
-// conv stage's marks are entries 210.. of each wave's row)
+// s_memtime timeline of the waves of workgroup 128 (rows 0 .. 7) and of
+// workgroup 127 (rows 8 .. 15: at T = 376 a last tile of 40 live rows, the
+// projection tail's !full path); probe builds only; the conv stage's marks
+// are entries 210.. of each wave's row
 SBK_PROBE_BUFFER(g_ffn_tl, 16, 256)
 #define FFN_TL(i) SBK_PROBE(if (tl_rec >= 0 && lane == 0) g_ffn_tl[tl_rec][i] = __builtin_amdgcn_s_memtime();)
 
@@ -394,7 +423,7 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
   const int SF = CHAIN ? 2 * S : S;                     // FFN K-steps (blocks A, B)
   const int SP = PROJ ? (a.np / TROWS) * K1 : 0;        // projection K-steps (image tiles after the FFN ones)
   const int ST = SF + SP;
-  SBK_PROBE(const int tl_rec = blockIdx.x == 128 ? w : -1;)
+  SBK_PROBE(const int tl_rec = blockIdx.x == 128 ? w : blockIdx.x == 127 ? NW + w : -1;)
   FFN_TL(0);
 
   // ---- weight tile s -> ring slot (LDS-DMA, 1 KB = 8 rows per wave-instruction)
@@ -848,9 +877,10 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
     lds_barrier();
     FFN_TL(205);
     // ---- projection y = u . Wp^T (bf16), 256 output columns per K1 steps.
-    // Stores go out T per step during the first MT steps of every column
-    // block, each right after that step's DMA issue: the out rows in block 0,
-    // block nc-1's y rows in block nc (the last block's after the loop).  A
+    // Stores go out during the first MT steps of every column block, each
+    // right after that step's DMA issue: the out rows in block 0 (T stores of
+    // 16 B per step), block nc-1's y rows in block nc (one 16-B store per
+    // step: proj_pair; the last block's after the loop).  A
     // tile wait counts the stores younger than its tile, so a store only has
     // to land before the wait two steps on instead of holding the next one
     // (a store counts in vmcnt like the LDS-DMA tiles).  Workgroups with rows
@@ -858,17 +888,21 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
     // block ends / the end and their waits assume none younger.  No reloads
     // past ST-1.
     static_assert(MT <= K1, "stores of a column block fit in its steps");
+    static_assert(T == 2, "a lane's two tiles of a row pair up into one 16-B store");
     const int ncp = a.np / TROWS;
     const bool full = m0 + BM <= mlim;
-    uint2 yq[T][MT];  // the previous column block's y (bf16)
+    // the previous column block's y (bf16): the 8 consecutive columns
+    // 32w + 16 (g & 1) + 8 (g >> 1) .. of row mt*16 + fr (proj_pair)
+    uint4 yq[MT];
+    // stores of step r of column block c
+    auto kst = [&](int c, int r) __attribute__((always_inline)) { return r < MT ? (c == 0 ? T : 1) : 0; };
     for (int nc = 0; nc < ncp; ++nc) {
 #pragma unroll
       for (int r = 0; r < K1; ++r) {
         const int s = SF + nc * K1 + r;
-        // stores of the two steps before (k(x) = T if step x stored)
-        const int kprev1 = (r >= 1 ? (r - 1 < MT) : (K1 - 1 < MT)) ? T : 0;
-        const int kprev2 = (r >= 2 ? (r - 2 < MT) : (K1 + r - 2 < MT)) ? T : 0;
-        const int k1 = (r >= 1 || nc > 0) ? kprev1 : 0, k2 = (r >= 2 || nc > 0) ? kprev2 : 0;
+        // stores of the two steps before (the first block has none before it)
+        const int k1 = r >= 1 ? kst(nc, r - 1) : nc > 0 ? kst(nc - 1, K1 - 1) : 0;
+        const int k2 = r >= 2 ? kst(nc, r - 2) : nc > 0 ? kst(nc - 1, K1 + r - 2) : 0;
         vm_wait((s + 1 < ST ? GL : 0) + (full ? k1 + k2 : 0));
         const bf16_t* tile = ring + (s % NB) * TROWS * BK;
         // fragment offsets from an opaque lane id (hoisted, they spill)
@@ -883,8 +917,10 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
             const int row = w * (T * 16) + t * 16 + lfr;
             fw[ks][t] = ld8(tile + row * BK + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 3));
           }
-        // the A operand from Xn each step (not held in VGPRs here: the
-        // registers go to the deferred stores instead)
+        // the A operand from Xn each step.  (Held in VGPRs for all column
+        // blocks, as phase 1 holds its operand: the 24 reads up front, with
+        // every wave behind the same barrier, cost the ~800 cycles the steps
+        // then saved; equal in the A/B, +13 .. 16 VGPRs: round 10.)
         bf16x8 fx[BK / 32][MT];
 #pragma unroll
         for (int ks = 0; ks < BK / 32; ++ks)
@@ -909,9 +945,8 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
             for (int j = 0; j < T; ++j)
               *reinterpret_cast<f32x4*>(a.out + row * D + (w * T + j) * 16 + 4 * lg) = ov[j];
           } else {
-#pragma unroll
-            for (int t = 0; t < T; ++t)
-              *reinterpret_cast<uint2*>(a.yp + row * a.np + (nc - 1) * TROWS + w * (T * 16) + t * 16 + 4 * lg) = yq[t][r];
+            *reinterpret_cast<uint4*>(a.yp + row * a.np + (nc - 1) * TROWS + w * (T * 16) + 16 * (lg & 1) + 8 * (lg >> 1)) =
+                yq[r < MT ? r : 0];
           }
         }
 #pragma unroll
@@ -925,18 +960,15 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
       int ln;
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
 #pragma unroll
-      for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const f32x4 v = acc1[t][mt];
-          yq[t][mt].x = pack_bf16x2(v[0], v[1]);
-          yq[t][mt].y = pack_bf16x2(v[2], v[3]);
-          acc1[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-          const int row = m0 + mt * 16 + (ln & 15);
-          if ((!full || nc == ncp - 1) && row < mlim)
-            *reinterpret_cast<uint2*>(a.yp + (long long)row * a.np + nc * TROWS + w * (T * 16) + t * 16 + 4 * (ln >> 4)) =
-                yq[t][mt];
-        }
+      for (int mt = 0; mt < MT; ++mt) {
+        yq[mt] = proj_pair(acc1[0][mt], acc1[1][mt]);
+        acc1[0][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc1[1][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int row = m0 + mt * 16 + (ln & 15), lg = ln >> 4;
+        if ((!full || nc == ncp - 1) && row < mlim)
+          *reinterpret_cast<uint4*>(a.yp + (long long)row * a.np + nc * TROWS + w * (T * 16) + 16 * (lg & 1) + 8 * (lg >> 1)) =
+              yq[mt];
+      }
     }
     FFN_TL(206);
     if (!full) {
