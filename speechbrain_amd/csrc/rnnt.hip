@@ -290,8 +290,18 @@ SBK_API int sbk_rnnt_backward(const float* x, const int* labels, int B, int T, i
 // Transducer decoding (decoders/transducer.py:137-377): log-softmax of the
 // joint logits and their top-k in one pass, one wave per row.  Replaces
 // LogSoftmax → torch.max (greedy, k = 1) / torch.topk (beam) on (rows, V).
-// Ties resolve to the lower vocabulary index.  vals = x[idx] - lse.
+// Ties resolve to the lower vocabulary index.  vals = x[idx] - lse.  NaN
+// entries rank after -inf, by index (their vals are NaN, as the row's lse).
 namespace {
+// Order-preserving int key of a float: a > b <=> key(a) > key(b), -0 and +0
+// share a key, every NaN maps to INT_MIN (below -inf).  topk_value inverts it.
+__device__ __forceinline__ int topk_key(float x) {
+  if (x != x) return (int)0x80000000;
+  const int b = __float_as_int(x);
+  return b >= 0 ? b : (b ^ 0x7fffffff) + (b == (int)0x80000000);  // -0: -1 -> 0
+}
+__device__ __forceinline__ float topk_value(int key) { return __int_as_float(key >= 0 ? key : key ^ 0x7fffffff); }
+
 __global__ void __launch_bounds__(256) logsoftmax_topk_kernel(const float* __restrict__ x, long long ldx, int R,
                                                               int V, int k, float* __restrict__ vals,
                                                               long long* __restrict__ idx) {
@@ -305,34 +315,38 @@ __global__ void __launch_bounds__(256) logsoftmax_topk_kernel(const float* __res
   float s = 0.f;
   for (int v = lane; v < V; v += 64) s += expf(xr[v] - m);
   const float lse = m + logf(wave_sum(s));
+  // Entries are ranked by an integer key that orders like the float (after
+  // -0 -> +0) and puts NaN last, below -inf: a row with fewer than k
+  // comparable entries still yields k distinct indices inside [0, V) — the
+  // NaN entries by ascending index — instead of the "none found" sentinel.
   int prev_i = -1;
-  float prev_v = INFINITY;
+  int prev_k = 0x7fffffff;
   for (int j = 0; j < k; ++j) {
-    // next best strictly after (prev_v, prev_i) in (value desc, index asc) order
-    float bv = -INFINITY;
+    // next best strictly after (prev_k, prev_i) in (key desc, index asc) order
+    int bk = (int)0x80000000;
     int bi = 0x7fffffff;
     for (int v = lane; v < V; v += 64) {
-      const float xv = xr[v];
-      const bool after = xv < prev_v || (xv == prev_v && v > prev_i);
-      if (after && (xv > bv || (xv == bv && v < bi))) {
-        bv = xv;
+      const int xk = topk_key(xr[v]);
+      const bool after = xk < prev_k || (xk == prev_k && v > prev_i);
+      if (after && (xk > bk || (xk == bk && v < bi))) {
+        bk = xk;
         bi = v;
       }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
+      const int ok = __shfl_xor(bk, o);
       const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
+      if (ok > bk || (ok == bk && oi < bi)) {
+        bk = ok;
         bi = oi;
       }
     }
     if (lane == 0) {
-      vals[(long long)row * k + j] = bv - lse;
+      vals[(long long)row * k + j] = topk_value(bk) - lse;
       idx[(long long)row * k + j] = bi;
     }
-    prev_v = bv;
+    prev_k = bk;
     prev_i = bi;
   }
 }
