@@ -8,7 +8,9 @@
 // the chain's residual layout — wave w, lane (g, fr): rows mt*16 + fr, units
 // (w*2 + j)*16 + 4g + e — and never leave the CU.
 //   phase -1: wave w owns 32 out_proj units (two 16-unit tiles) of the 80
-//             staged frames; wo fragments straight from global (L2);
+//             staged frames; wo fragments straight from global (L2), o first
+//             across the workgroup, the second half of wo and all of x
+//             issued behind the MFMAs of the K-steps;
 //   phase 1 : wave w owns GLU groups 2w and 2w + 1 (64 permuted rows of
 //             W1p): the U fragments of a K-step are read once per 64 weight
 //             rows instead of once per 32;
@@ -47,6 +49,13 @@ constexpr int CS_NW = FFN_NW, CS_NT = FFN_NT;
 constexpr int CS_S = CS_D + FFN_PAD;  // U / G row stride: rows swizzled by ffn_sw, as Xn / Hs
 constexpr int CS_TILE = 256 * 64;     // elements of an image tile
 constexpr int CS_P1T = 8, CS_P3T = 4; // image tiles of phase 1 (4 K-steps x 2 group halves) and phase 3
+// out_proj K-steps (of 8) whose wo fragments are issued before o is staged.
+// Same-box A/B of the step (ms): 1 1.0928, 2 1.0909, 4 1.0882, 8 1.0980
+// against 1.1075; a probe build may override it
+#ifndef CS_WO_AHEAD
+#define CS_WO_AHEAD 4
+#endif
+static_assert(CS_WO_AHEAD >= 1 && CS_WO_AHEAD <= CS_D / 32, "K-steps of out_proj");
 // LDS (bytes): U/V, G, the fp32 conv tile; ring slot 0 over G, slot 1 over the conv tile's front
 constexpr int CS_OFF_G = CS_ROWS * CS_S * 2, CS_OFF_CV = 2 * CS_OFF_G;
 constexpr int CS_LDS = CS_OFF_CV + CS_BM * CS_D * 4;
@@ -140,25 +149,48 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     constexpr int RS = CS_NW + 4;  // partial-row stride (floats), 16-B aligned
     static_assert(CS_TILE / 2 + 2 * CS_ROWS * RS + 2 * CS_ROWS + 2 * CS_D <= CS_BM * CS_D, "LN0 scratch fits");
     float* gb0s = lnscr + 2 * CS_ROWS * RS + 2 * CS_ROWS;  // [g0 | b0]
-    const float4 gbv = tid < CS_D / 2 ? *reinterpret_cast<const float4*>((tid < CS_D / 4 ? a.g0 : a.b0) +
-                                                                         4 * (tid % (CS_D / 4)))
-                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+    // unconditional, as bo below (threads CS_D / 2.. read b0 again and drop it):
+    // a load under a branch is merged with its zero by a register copy, and
+    // the compiler puts s_waitcnt vmcnt(0) in front of the copy, in the
+    // middle of the burst
+    const float4 gbv = *reinterpret_cast<const float4*>((tid < CS_D / 4 ? a.g0 : a.b0) + 4 * (tid % (CS_D / 4)));
     // wave w: units (w*2 + j)*16 .. +15 of all CS_MT1 frame tiles; D[unit 4g + e][frame mt*16 + fr]
     float4 xv[2][CS_MT1], bo4[2];
     bf16x8 fwo[2][CS_D / 32];
+    const float* bop = a.bo ? a.bo : a.g0;  // a null bo reads g0 instead and is zeroed at the residual add
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int u0 = (w * 2 + j) * 16 + 4 * g;
+    for (int j = 0; j < 2; ++j) bo4[j] = *reinterpret_cast<const float4*>(bop + (w * 2 + j) * 16 + 4 * g);
+    // The first data barrier needs o and the parameter rows only, and a wave
+    // reaches it only after it has issued every load in front of it: the
+    // CU's one vector-memory queue returns in order and issue stalls while
+    // it is full.  So: a bare s_barrier (it waits for no data) puts every
+    // wave's o requests ahead of any wave's wo request; only the wo
+    // fragments of the first CS_WO_AHEAD K-steps are issued before o is
+    // staged; the rest of wo and all of x (needed only at the residual add)
+    // are issued K-step by K-step behind the MFMAs.  All plain loads, their
+    // order in the instruction stream held by sched_barrier, so the
+    // compiler's own counted vmcnt waits start K-step kk when its two
+    // fragments are in.
+    constexpr int KS = CS_D / 32;
+    auto ld_wo = [&](int kk) __attribute__((always_inline)) {
 #pragma unroll
-      for (int mt = 0; mt < CS_MT1; ++mt) {
-        const int f = min(max(f0 + mt * 16 + fr, 0), a.T - 1);
-        xv[j][mt] = *reinterpret_cast<const float4*>(a.x + (ubase + f) * CS_D + u0);
-      }
-      bo4[j] = a.bo ? *reinterpret_cast<const float4*>(a.bo + u0) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const bf16_t* wrowo = a.wo + (long long)((w * 2 + j) * 16 + fr) * CS_D + fk;
+      for (int j = 0; j < 2; ++j) fwo[j][kk] = ld8(a.wo + (long long)((w * 2 + j) * 16 + fr) * CS_D + fk + kk * 32);
+    };
+    auto ld_x = [&](int i) __attribute__((always_inline)) {
+      const int j = i / CS_MT1, mt = i - j * CS_MT1;
+      const int f = min(max(f0 + mt * 16 + fr, 0), a.T - 1);
+      xv[j][mt] = *reinterpret_cast<const float4*>(a.x + (ubase + f) * CS_D + (w * 2 + j) * 16 + 4 * g);
+    };
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int kk = 0; kk < CS_D / 32; ++kk) fwo[j][kk] = ld8(wrowo + kk * 32);
+    for (int kk = 0; kk < CS_WO_AHEAD; ++kk) {
+      ld_wo(kk);
+      __builtin_amdgcn_sched_barrier(0);  // K order, not address order
     }
+    SBK_PROBE(for (int i = 0; i < OC; ++i) asm volatile("" : "+v"(ov[i].x));)
+    CS_TL(9);  // o landed
 #pragma unroll
     for (int i = 0; i < OC; ++i) {
       const int c = tid + i * CS_NT;
@@ -175,14 +207,28 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) acc[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SBK_PROBE(asm volatile("" : "+v"(fwo[0][0]), "+v"(fwo[1][0]));)
+    CS_TL(10);  // the first K-step's wo fragments landed: first MFMA
 #pragma unroll
-    for (int kk = 0; kk < CS_D / 32; ++kk)
+    for (int kk = 0; kk < KS; ++kk) {
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) {
         const bf16x8 fo = *reinterpret_cast<const bf16x8*>(Gs + (mt * 16 + fr) * CS_S + kk * 32 + fks);
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[j][mt] = FFN_MFMA(fwo[j][kk], fo, acc[j][mt]);
       }
+      // K-step kk + 1 stays behind K-step kk, and behind the loads issued in between
+      __builtin_amdgcn_sched_barrier(0);
+      if (kk + CS_WO_AHEAD < KS) ld_wo(kk + CS_WO_AHEAD);
+#pragma unroll
+      for (int i = kk * (2 * CS_MT1) / KS; i < (kk + 1) * (2 * CS_MT1) / KS; ++i) ld_x(i);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    SBK_PROBE(asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__float_as_int(acc[1][CS_MT1 - 1][0]))));)
+    CS_TL(11);  // last MFMA retired
+    SBK_PROBE(for (int j = 0; j < 2; ++j) for (int mt = 0; mt < CS_MT1; ++mt) asm volatile("" : "+v"(xv[j][mt].x));)
+    CS_TL(12);  // x landed
+    if (!a.bo) bo4[0] = bo4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
     float xa[2][CS_MT1][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j)

@@ -99,6 +99,17 @@
 // 73.9 -> 72.4 us.  Holding u's fragments in VGPRs for the 12 steps (as phase
 // 1 does) was measured on top and alone: no gain either way (DESIGN section
 // 3, round 10).
+// Round 11: the start of the conv stage (convstage.h, phase -1: 22.6k of the
+// chain launch's 152.7k cycles before the first useful MFMA result).  Two
+// loads under a branch (the LN0 affine, the out_proj bias) each drew an
+// s_waitcnt vmcnt(0) into the middle of the launch-start burst, the second
+// in front of half of wo; and a wave reached the first barrier, which needs
+// o only, after issuing all 31 of its loads into a queue that stalls when
+// full.  Now: unconditional loads, o first across the workgroup (a bare
+// s_barrier), wo of four K-steps ahead, the rest of wo and x issued behind
+// the MFMAs under the compiler's counted waits.  The stretch ends at 18.1k
+// cycles instead of 25.0k in the probe build, the same bits;
+// conv_chain_kernel<1> and the step: DESIGN section 3, round 11.
 #include "mfma.h"
 
 using namespace sbk;
