@@ -923,6 +923,41 @@ int sbk_embed_gather(const int* ids, const float* weight, int N, int V, int D, f
 int sbk_segsum_rows(const float* src, const long long* order, const long long* offs, long long items, int ncodes,
                     int D, float* out, void* stream);
 
+/* ---- lstm.hip: LSTM recurrence (nnet/RNN.py:169-277), one or two directions ---- */
+
+/* The T forward launches of one LSTM layer (torch.nn.LSTM semantics, gate
+ * order i, f, g, o), D = 1 or 2 directions in the same launches: launch s
+ * works on time s in direction 0 and T-1-s in direction 1.  bf16 != 0: w_hh
+ * (D, 4H, H) is bf16 and the h operand is rounded to bf16; else fp32 and
+ * exact-fp32 MFMA.  The (h, c) state is fp32 in both.  Input
+ * pre-activations: gi (B, T, D, 4H) fp32 with b_ih already added, or tok
+ * (B, T) int32 token ids with table = the stacked W_ih transposed
+ * (I, D, 4H) fp32 and b_ih (D, 4H) or null — token `blank` adds b_ih only,
+ * ids above it read row id - 1.  Exactly one of gi / tok.  b_hh (D, 4H) or
+ * null; hx, cx (D, B, H) or null (zeros); lens (B) int32 = steps per row, or
+ * null: a row keeps (h, c) at every t >= lens[b] and its y rows are zero
+ * there, so the reverse direction carries (hx, cx) through the padding.
+ * hstate, cstate (B, T, D*H) = the carried state after every step; y
+ * (B, T, D*H) or null; save (B, T, D, 4H) or null = i, f, g, o for the
+ * backward.  Any B, T, H, I >= 1.  A null required pointer, a size <= 0, D
+ * outside {1, 2}, both or neither of gi / tok, D*4*H*H or 4*B*T*D past
+ * int32: 1001. */
+int sbk_lstm_fwd(int bf16, int D, const void* w_hh, const float* b_hh, const float* hx, const float* cx,
+                 const float* gi, const int* tok, int blank, const float* table, int I, const float* b_ih,
+                 const int* lens, int B, int T, int H, float* hstate, float* cstate, float* y, float* save,
+                 void* stream);
+
+/* The T backward launches (order mirrored per direction) and one more for
+ * the carry into dhx, dcx.  w_hhT = W_hh^T per direction (D, H, 4H) in the
+ * compute dtype; cx, cstate, save, lens as given to / written by
+ * sbk_lstm_fwd; dy (B, T, D*H) or null; dhn, dcn (D, B, H) or null.  Writes
+ * dG (B, T, D, 4H) fp32 — the gradient of the gate pre-activations, of gi and
+ * of the recurrent product alike, zero past a row's length — and dhx, dcx
+ * (D, B, H).  dw (2, 2, D, B, H) fp32 is scratch.  No atomics. */
+int sbk_lstm_bwd(int bf16, int D, const void* w_hhT, const float* cx, const float* cstate, const float* save,
+                 const float* dy, const float* dhn, const float* dcn, const int* lens, int B, int T, int H,
+                 float* dG, float* dw, float* dhx, float* dcx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

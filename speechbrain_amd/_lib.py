@@ -148,6 +148,10 @@ SIGNATURES = {
     "sbk_embed_onehot": [_vp, _i, _i, _i, _vp, _vp],
     "sbk_embed_gather": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "sbk_segsum_rows": [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp],
+    # lstm.hip (LSTM recurrence, one launch per step for both directions)
+    "sbk_lstm_fwd": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp,
+                     _vp],
+    "sbk_lstm_bwd": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     # attention.hip
     "sbk_relpos_attention":[_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],

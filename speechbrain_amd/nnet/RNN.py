@@ -1,5 +1,7 @@
-"""Drop-in for speechbrain.nnet.RNN.GRU (RNN.py:280-388) on HIP: the
-transducer recipes' prediction network `dec`.
+"""Drop-ins for speechbrain.nnet.RNN.GRU (RNN.py:280-388) and LSTM
+(RNN.py:169-277) on HIP.  The GRU, the transducer recipes' prediction network
+`dec`, is described here; the LSTM (one or two directions, csrc/lstm.hip) by
+the docstring of its class below.
 
 Same constructor, forward(x, hx=None, lengths=None) -> (output, hn) and
 state_dict keys (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0,
@@ -20,8 +22,8 @@ pad_packed_sequence pair: row b runs int(lengths[b] * T) steps, its later
 outputs are zero, hn is its last valid state and the output is cut to the
 longest row.  Implemented as a per-row step mask inside the kernels.
 
-Unidirectional only (`bidirectional=True` raises NotImplementedError); device
-tensors only (SbkError, no fallback).
+The GRU is unidirectional only (`bidirectional=True` raises
+NotImplementedError); device tensors only (SbkError, no fallback).
 """
 import torch
 
@@ -201,3 +203,200 @@ class GRU(torch.nn.Module):
             if layer < L - 1 and rnn.dropout > 0:
                 y = A.dropout(y, rnn.dropout, self.training)
         return y, torch.stack(hns, 0)
+
+
+class _LSTMLayerFn(torch.autograd.Function):
+    """One LSTM layer over a sequence, D = 1 or 2 directions in the same
+    launches.  x (B, T, I) or None with tok (B, T) int32 one-hot token ids;
+    h0, c0 (D, B, H) or None; lens (B,) int32 or None; weights: per direction
+    w_ih (4H, I), w_hh (4H, H), b_ih, b_hh (4H) or None.  Returns the output
+    (B, T, D * H) and hn, cn (D, B, H)."""
+
+    @staticmethod
+    def forward(ctx, x, tok, blank, h0, c0, lens, dtype, cache, key, D, *weights):
+        w_ih, w_hh = list(weights[0::4]), list(weights[1::4])
+        b_ih, b_hh = list(weights[2::4]), list(weights[3::4])
+        H4, I = w_ih[0].shape
+        H = H4 // 4
+        dev = w_hh[0].device
+        bf = int(dtype == _bf16)
+        need = any(ctx.needs_input_grad)
+        # kernel copies, the directions stacked: W_hh (D, 4H, H), W_ih (D * 4H, I), biases (D * 4H)
+        whh = cache.get(key + "hh" + str(bf), w_hh, lambda: _enc.to_compute(
+            torch.stack([w.detach() for w in w_hh]), dtype))
+        bih = None if b_ih[0] is None else torch.cat([b.detach() for b in b_ih])
+        bhh = None if b_hh[0] is None else torch.cat([b.detach() for b in b_hh])
+        hx0 = None if h0 is None else h0.detach().float().contiguous()
+        cx0 = None if c0 is None else c0.detach().float().contiguous()
+        a = wk = gi = table = xs = None
+        if tok is not None:
+            B, T = tok.shape
+            # the stacked W_ih transposed (I, D * 4H) fp32, holding the compute dtype's values
+            table = cache.get(key + "tab" + str(bf), w_ih, lambda: (
+                torch.cat([w.detach() for w in w_ih]).to(dtype).float().t().contiguous()))
+        else:
+            B, T = x.shape[:2]
+            vec = 8 if bf else 4
+            Kp = -(-I // vec) * vec
+            # K zero-padded to the GEMM's 16-byte vectors: one GEMM gives both directions' gi
+            wk = cache.get(key + "ih" + str(bf), w_ih, lambda: _enc.to_compute(
+                torch.nn.functional.pad(torch.cat([w.detach() for w in w_ih]), (0, Kp - I)), dtype))
+            xs = x.detach().reshape(B * T, I)
+            a = _enc.to_compute(xs, dtype)
+            if Kp != I:
+                a = torch.nn.functional.pad(a, (0, Kp - I))
+            gi = _enc.gemm(a, wk, bias=bih)
+        hstate = torch.empty(B, T, D * H, device=dev, dtype=_f32)
+        cstate = torch.empty(B, T, D * H, device=dev, dtype=_f32)
+        y = hstate if lens is None else torch.empty(B, T, D * H, device=dev, dtype=_f32)
+        save = torch.empty(B, T, D, 4 * H, device=dev, dtype=_f32) if need else None
+        check(lib().sbk_lstm_fwd(bf, D, ptr(whh), ptr(bhh), ptr(hx0), ptr(cx0), ptr(gi), ptr(tok), int(blank),
+                                 ptr(table), I, ptr(bih) if tok is not None else None, ptr(lens), B, T, H,
+                                 ptr(hstate), ptr(cstate), ptr(y) if lens is not None else None, ptr(save),
+                                 stream_of(hstate)), "sbk_lstm_fwd")
+        # the carried state makes the last step of either scan the final state of every row
+        ends = [(T - 1, 0)] if D == 1 else [(T - 1, 0), (0, H)]
+        hn = torch.stack([hstate[:, t, o:o + H] for t, o in ends])
+        cn = torch.stack([cstate[:, t, o:o + H] for t, o in ends])
+        if need:
+            ctx.save_for_backward(hstate, cstate, save, hx0, cx0, lens, xs, wk, tok)
+            ctx.cfg = (dtype, cache, key, blank, B, T, H, I, D, w_hh, None if x is None else x.dtype)
+            ctx.has = (b_ih[0] is not None, b_hh[0] is not None, h0 is not None, c0 is not None)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, dy, dhn, dcn):
+        hstate, cstate, save, hx0, cx0, lens, xs, wk, tok = ctx.saved_tensors
+        dtype, cache, key, blank, B, T, H, I, D, w_hh, xdt = ctx.cfg
+        has_bih, has_bhh, has_h0, has_c0 = ctx.has
+        dev = hstate.device
+        bf = int(dtype == _bf16)
+        whhT = cache.get(key + "hhT" + str(bf), w_hh, lambda: _enc.to_compute(
+            torch.stack([w.detach().t() for w in w_hh]), dtype))
+        dy = None if dy is None else dy.detach().float().contiguous()
+        dhn = None if dhn is None else dhn.detach().float().contiguous()
+        dcn = None if dcn is None else dcn.detach().float().contiguous()
+        dG = torch.empty(B, T, D, 4 * H, device=dev, dtype=_f32)
+        dw = torch.empty(2, 2, D, B, H, device=dev, dtype=_f32)
+        dhx = torch.empty(D, B, H, device=dev, dtype=_f32)
+        dcx = torch.empty(D, B, H, device=dev, dtype=_f32)
+        check(lib().sbk_lstm_bwd(bf, D, ptr(whhT), ptr(cx0), ptr(cstate), ptr(save), ptr(dy), ptr(dhn), ptr(dcn),
+                                 ptr(lens), B, T, H, ptr(dG), ptr(dw), ptr(dhx), ptr(dcx), stream_of(hstate)),
+              "sbk_lstm_bwd")
+        g2 = dG.view(B * T, D * 4 * H)
+        need = ctx.needs_input_grad
+        nw = 10                      # position of the first weight among forward's inputs
+        grads = [None] * (4 * D)
+        dx = None
+        for d in range(D):
+            if need[nw + 4 * d + 1]:
+                first = hx0[d].unsqueeze(1) if hx0 is not None else torch.zeros(B, 1, H, device=dev, dtype=_f32)
+                hd = hstate[:, :, d * H:(d + 1) * H]
+                # the h each step started from: the reverse scan's carried padding makes
+                # [state[:, 1:], h0] right for ragged rows
+                hprev = torch.cat([first, hd[:, :T - 1]] if d == 0 else [hd[:, 1:], first], 1).reshape(B * T, H)
+                gd = dG[:, :, d].reshape(B * T, 4 * H)
+                grads[4 * d + 1] = A.wgrad(A._as(gd, dtype), A._as(hprev, dtype))
+        want_ih = any(need[nw + 4 * d] for d in range(D))
+        if tok is not None:
+            if want_ih:
+                # per-token sum of the dG rows: rows of d(W_ih^T); the blank has none
+                dw_ih = segsum_rows(g2, _rows_of_tokens(tok, blank, I), I).t().contiguous()
+        else:
+            if want_ih:
+                # fp32 operands in both modes, as in the GRU (DESIGN.md)
+                dw_ih = A.wgrad(g2, xs.float())
+            if need[0]:
+                dx = A.dgrad(A._as(g2, dtype), wk)[:, :I].reshape(B, T, I).to(xdt)
+        if want_ih:
+            for d in range(D):
+                grads[4 * d] = dw_ih[d * 4 * H:(d + 1) * 4 * H]
+        if has_bih or has_bhh:
+            db = A.rowsum(g2)        # dgi and dgh are the same rows: one sum serves b_ih and b_hh
+            for d in range(D):
+                if has_bih and need[nw + 4 * d + 2]:
+                    grads[4 * d + 2] = db[d * 4 * H:(d + 1) * 4 * H]
+                if has_bhh and need[nw + 4 * d + 3]:
+                    grads[4 * d + 3] = db[d * 4 * H:(d + 1) * 4 * H].clone()
+        return (dx, None, None, dhx if has_h0 and need[3] else None, dcx if has_c0 and need[4] else None,
+                None, None, None, None, None, *grads)
+
+
+class LSTM(torch.nn.Module):
+    """Drop-in for speechbrain.nnet.RNN.LSTM (RNN.py:169-277) on HIP
+    (csrc/lstm.hip): forward(x, hx=None, lengths=None) -> (output, (hn, cn)),
+    one or two directions, torch's state_dict keys (`_reverse` suffixes) and
+    gate order i, f, g, o.  `self.rnn` is a torch.nn.LSTM used as the parameter
+    container only.  Per layer: one MFMA GEMM gives both directions' input
+    pre-activations (or none, for a tagged one-hot Embedding input to layer 0),
+    then one launch per time step runs both directions' recurrence; layers
+    >= 1 read the 2H-wide output.  fp32 by default, bf16 operands with fp32
+    (h, c) state under torch.autocast(bf16).  `lengths` as in the GRU: a
+    per-row step mask, mirrored for the reverse direction, which reproduces
+    torch's packed sequences.  Device tensors only (SbkError, no fallback)."""
+
+    def __init__(self, hidden_size, input_shape=None, input_size=None, num_layers=1, bias=True, dropout=0.0,
+                 re_init=True, bidirectional=False):
+        super().__init__()
+        self.reshape = False
+        if input_shape is None and input_size is None:
+            raise ValueError("Expected one of input_shape or input_size.")
+        if input_size is None:
+            if len(input_shape) > 3:
+                self.reshape = True
+            input_size = torch.prod(torch.tensor(input_shape[2:])).item()
+        # parameter container: torch's names and init; its forward is never called
+        self.rnn = torch.nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
+                                 dropout=dropout, bidirectional=bidirectional, bias=bias, batch_first=True)
+        if re_init:
+            rnn_init(self.rnn)
+        self._wc = _enc.WeightCache()
+
+    _steps = staticmethod(GRU._steps)
+
+    def forward(self, x, hx=None, lengths=None):
+        if self.reshape and x.ndim == 4:
+            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
+        rnn = self.rnn
+        if hx is not None and not (isinstance(hx, (tuple, list)) and len(hx) == 2):
+            raise ValueError("hx must be a tuple (h0, c0)")
+        h0, c0 = (None, None) if hx is None else hx
+        if x.ndim != 3 or x.shape[-1] != rnn.input_size:
+            raise ValueError(f"LSTM expects (batch, time, {rnn.input_size}) (got {tuple(x.shape)})")
+        B, T, _ = x.shape
+        L, H, D = rnn.num_layers, rnn.hidden_size, 2 if rnn.bidirectional else 1
+        for s in (h0, c0):
+            if hx is not None and (not torch.is_tensor(s) or tuple(s.shape) != (L * D, B, H)):
+                raise ValueError(f"hx must be two tensors of {(L * D, B, H)} "
+                                 f"(got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__})")
+        require_device(x, h0, c0, rnn.weight_hh_l0)
+        tag = getattr(x, "_sbk_onehot", None)
+        tok = blank = None
+        if tag is not None and tag[2] == x._version and tuple(tag[0].shape) == (B, T):
+            tok, blank = tag[0], tag[1]   # unmodified one-hot rows: layer 0 never reads x
+        lens = None
+        if lengths is not None:
+            steps = self._steps(lengths, T)
+            Tn = int(steps.max())
+            if Tn < T:
+                x = x[:, :Tn]
+                tok = None if tok is None else tok[:, :Tn].contiguous()
+                T = Tn
+            if int(steps.min()) < T:
+                lens = steps.to(device=x.device, dtype=torch.int32)
+        dtype = _enc.compute_dtype()
+        y, hns, cns = x, [], []
+        for layer in range(L):
+            w = [getattr(rnn, f"{n}_l{layer}{sfx}", None) for sfx in ("", "_reverse")[:D]
+                 for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+            hl = None if hx is None else h0[layer * D:(layer + 1) * D]
+            cl = None if hx is None else c0[layer * D:(layer + 1) * D]
+            if layer == 0 and tok is not None:
+                y, hn, cn = _LSTMLayerFn.apply(None, tok, blank, hl, cl, lens, dtype, self._wc, f"l{layer}", D, *w)
+            else:
+                y, hn, cn = _LSTMLayerFn.apply(y, None, 0, hl, cl, lens, dtype, self._wc, f"l{layer}", D, *w)
+            hns.append(hn)
+            cns.append(cn)
+            if layer < L - 1 and rnn.dropout > 0:
+                y = A.dropout(y, rnn.dropout, self.training)
+        return y, (torch.cat(hns, 0), torch.cat(cns, 0))
