@@ -880,7 +880,7 @@ int sbk_gumbel_vq_bwd(const float* dout, const float* vars, const float* logits,
                       const float* gpsum, float tau, const long long* order, const long long* offs, int Rq, int G,
                       int V, int ncodes, int D, float* dlogits, float* dvars, void* stream);
 
-/* ---- gru.hip: GRU recurrence (nnet/RNN.py:280-388) and Embedding (nnet/embedding.py) ---- */
+/* ---- gru.hip: GRU recurrence (nnet/RNN.py:280-388) ---- */
 
 /* The T forward steps of one GRU layer, one launch per step (torch.nn.GRU
  * semantics, gate order r, z, n).  bf16 != 0: w_hh (3H, H) is bf16 and the
@@ -907,6 +907,8 @@ int sbk_gru_fwd(int bf16, const void* w_hh, const float* b_hh, const float* hx, 
 int sbk_gru_bwd(int bf16, const void* w_hhT, const float* hx, const float* state, const float* save, const float* dy,
                 const float* dhn, const int* lens, int B, int T, int H, float* dgi, float* dgh, float* dhw,
                 float* dhx, void* stream);
+
+/* ---- embedding.hip: Embedding (nnet/embedding.py) ---- */
 
 /* out (N, V-1) fp32: the one-hot rows of ids (N) int32 as Embedding(
  * consider_as_one_hot=True) returns them: a zero row for `blank`, ids above

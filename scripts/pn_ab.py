@@ -118,7 +118,7 @@ def trace(arm, args, log, outdir):
         log(f"    {float(x['TotalDurationNs']) / n / 1e6:8.3f} ms/step {int(x['Calls']) / n:8.1f} calls/step  "
             f"{x['Name'][:110]}")
     if mine:
-        log(f"  gru.hip kernels: {sum(int(x['Calls']) for x in mine) / n:.0f} launches, "
+        log(f"  gru.hip / embedding.hip kernels: {sum(int(x['Calls']) for x in mine) / n:.0f} launches, "
             f"{sum(float(x['TotalDurationNs']) for x in mine) / n / 1e6:.3f} ms per step")
     return {"launches_per_step": calls / n, "kernel_ms_per_step": total / n / 1e6}
 

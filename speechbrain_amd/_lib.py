@@ -142,9 +142,10 @@ SIGNATURES = {
     "sbk_gumbel_vq_parts": [_i, _i],
     "sbk_gumbel_vq_fwd": [_vp, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "sbk_gumbel_vq_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    # gru.hip (GRU recurrence, one launch per step; Embedding gather / one-hot / segment sum)
+    # gru.hip (GRU recurrence, one launch per step)
     "sbk_gru_fwd": [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "sbk_gru_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    # embedding.hip (Embedding gather / one-hot / segment sum)
     "sbk_embed_onehot": [_vp, _i, _i, _i, _vp, _vp],
     "sbk_embed_gather": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "sbk_segsum_rows": [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp],

@@ -1,82 +1,37 @@
 // GRU recurrence of the transducer prediction network (nnet/RNN.py:280-388 of
-// the reference, torch.nn.GRU semantics, gate order r, z, n) and the kernels
-// of the Embedding drop-in (nnet/embedding.py:14-114).
+// the reference, torch.nn.GRU semantics, gate order r, z, n).
 //
 //   r = sigmoid(gi_r + W_hr h + b_hr)        z = sigmoid(gi_z + W_hz h + b_hz)
 //   q = W_hn h + b_hn                        n = tanh(gi_n + r * q)
 //   h_t = (1 - z) * n + z * h_{t-1}
 //
-// One launch per time step, forward and backward; the dependency between
-// steps is stream order.  No persistent kernel, no grid barrier, no flag
-// between workgroups, no float atomics.  sbk_gru_fwd / sbk_gru_bwd enqueue
-// the T launches of a sequence from the host side of the library, so a
-// sequence costs one call into the library.
+// One launch per time step on the skeleton of rnnstep.h: grid (ceil(H / 16),
+// ceil(B / 32)), the recurrent product dealt to eight waves and summed in
+// wave order.  sbk_gru_fwd / sbk_gru_bwd enqueue the launches of a sequence.
 //
-// Forward step t, grid (ceil(H / 16), ceil(B / 32)), 8 waves.  A workgroup
-// owns 16 hidden units and up to 32 batch rows: the three 16-column tiles
-// W_hh[g * H + j0 .. j0 + 16, :] (g = r, z, n) are MFMA B operands read from
-// memory as they are (8 consecutive K elements per lane), h_{t-1} rows are the
-// A operand (fp32 state, rounded to bf16 in bf16 mode; exact-fp32 MFMA in
-// fp32 mode).  The K range is dealt to the eight waves in 32-element chunks;
-// their partial tiles meet in LDS and are added in wave order.  The epilogue
-// adds the input pre-activations — rows of the dense gi (B, T, 3H), or rows of
-// the W_ih^T table gathered by token id (one-hot input; the blank adds b_ih
-// only) — applies the gates and writes h_t.  Step t reads state[:, t-1, :]
-// (hx at t = 0) and writes state[:, t, :]: nothing is updated in place.
-// With lengths, a row with t >= len_b keeps its state (state[b, t] =
+// Forward step t.  The product is h_{t-1} against the three 16-column tiles
+// W_hh[g * H + j0 .. j0 + 16, :] (g = r, z, n).  The epilogue adds the input
+// pre-activations — rows of the dense gi (B, T, 3H), or rows of the W_ih^T
+// table gathered by token id (one-hot input; the blank adds b_ih only) —
+// applies the gates and writes h_t.  Step t reads state[:, t-1, :] (hx at
+// t = 0) and writes state[:, t, :]: nothing is updated in place.  With
+// lengths, a row with t >= len_b keeps its state (state[b, t] =
 // state[b, t-1]) and its output row y[b, t] is zero.  When training, r, z, n
 // and q are kept in save (B, T, 4, H).
 //
 // Backward step t = T-1 .. 0, same grid.  The workgroup of units J forms
 //   dh_t[:, J] = dy_t[:, J] + z_{t+1} * dh_{t+1}[:, J] + dgh_{t+1} . W_hh[:, J]
-// (the product on MFMA against W_hh^T (H, 3H), K = 3H dealt to the waves; a
-// row masked at t+1 passes dh_{t+1} through), then the gate gradients of its
-// units from the saved activations, and writes dgi_t, dgh_t = (dr, dz, dn * r).
-// One more launch of the carry part alone gives dhx.  dh ping-pongs between
-// the two halves of a (2, B, H) buffer.
-#include "mfma.h"
+// (the product against W_hh^T (H, 3H), K = 3H; a row masked at t+1 passes
+// dh_{t+1} through), then the gate gradients of its units from the saved
+// activations, and writes dgi_t, dgh_t = (dr, dz, dn * r).  One more launch
+// of the carry part alone gives dhx.  dh ping-pongs between the two halves of
+// a (2, B, H) buffer.
+#include "rnnstep.h"
 
 using namespace sbk;
+using namespace sbk::rnnstep;
 
 namespace {
-
-constexpr int kThreads = 512;
-constexpr int kWaves = 8;
-constexpr int kSlice = 16;  // hidden units of a workgroup: one MFMA tile
-constexpr int kRows = 32;   // batch rows of a workgroup
-constexpr int kRowThreads = 256;  // the row kernels of the Embedding
-constexpr int kMT = kRows / 16;
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// 8 elements row[k0 .. k0 + 8) of a K-element row as an MFMA fragment, zero
-// past K.  vec: the row start and K allow 16-byte reads.
-template <typename T>
-__device__ __forceinline__ typename MT<T>::frag load_w8(const T* row, int k0, int K, bool vec) {
-  if (vec && k0 + 8 <= K) return MT<T>::load(row + k0);
-  float v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = k0 + i < K ? MT<T>::to_f32(row[k0 + i]) : 0.f;
-  return MT<T>::from8(v);
-}
-
-// the same from an fp32 row, converted to T
-template <typename T>
-__device__ __forceinline__ typename MT<T>::frag load_f8(const float* row, int k0, int K, bool vec) {
-  float v[8];
-  if (vec && k0 + 8 <= K) {
-    const float4 a = *reinterpret_cast<const float4*>(row + k0);
-    const float4 b = *reinterpret_cast<const float4*>(row + k0 + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = k0 + i < K ? row[k0 + i] : 0.f;
-  }
-  return MT<T>::from8(v);
-}
-
-__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct FwdArgs {
   const void* w_hh;      // (3H, H) in the compute dtype
@@ -104,46 +59,10 @@ __global__ void __launch_bounds__(kThreads) gru_fwd_step_kernel(FwdArgs a, int t
   const int mts = (nrows + 15) >> 4;
   const float* hprev = t == 0 ? a.hx : a.state + (long long)(t - 1) * H;
   const long long ldh = t == 0 ? H : (long long)Tn * H;
-  const bool vec_h = a.vec_h;
 
   f32x4 acc[kMT][3];
-#pragma unroll
-  for (int m = 0; m < kMT; ++m)
-#pragma unroll
-    for (int g = 0; g < 3; ++g) acc[m][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (hprev) {
-    const T* W = static_cast<const T*>(a.w_hh);
-    const int unit = j0 + (lane & 15);
-#pragma unroll 2
-    for (int k0 = w * 32; k0 < H; k0 += kWaves * 32) {
-      const int kk = k0 + 8 * (lane >> 4);
-      typename MT<T>::frag bw[3];
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-        bw[g] = unit < H ? load_w8<T>(W + ((long long)g * H + unit) * H, kk, H, a.vec_w) : MT<T>::zero();
-#pragma unroll
-      for (int m = 0; m < kMT; ++m) {
-        if (m < mts) {
-          const int row = b0 + m * 16 + (lane & 15);
-          const typename MT<T>::frag af =
-              row < B ? load_f8<T>(hprev + row * ldh, kk, H, vec_h) : MT<T>::zero();
-#pragma unroll
-          for (int g = 0; g < 3; ++g) MT<T>::mma(acc[m][g], af, bw[g]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < kMT; ++m) {
-    if (m < mts) {
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[w][g][m * 16 + 4 * (lane >> 4) + r][lane & 15] = acc[m][g][r];
-    }
-  }
-  __syncthreads();
+  product<T, 3>(acc, static_cast<const T*>(a.w_hh), H, H, hprev, ldh, j0, b0, B, H, mts, a.vec_w, a.vec_h, lane, w);
+  meet<3>(red, acc, mts, lane, w);
 
   const long long H3 = 3LL * H;
   for (int e = tid; e < nrows * kSlice; e += kThreads) {
@@ -153,16 +72,13 @@ __global__ void __launch_bounds__(kThreads) gru_fwd_step_kernel(FwdArgs a, int t
     float gh[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
-      float s = red[0][g][rr][jj];
-#pragma unroll
-      for (int ww = 1; ww < kWaves; ++ww) s += red[ww][g][rr][jj];
+      const float s = total<3>(red, g, rr, jj);
       gh[g] = a.b_hh ? s + a.b_hh[g * H + j] : s;
     }
     const long long bt = (long long)b * Tn + t;
     float gi[3];
     if (a.tok) {
-      const int v = a.tok[bt];
-      const int idx = v == a.blank ? -1 : (v < a.blank ? v : v - 1);
+      const int idx = token_row(a.tok[bt], a.blank);
       const bool hit = idx >= 0 && idx < a.I;
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
@@ -211,7 +127,7 @@ struct BwdArgs {
 // t in [-1, T-1]; t = -1 computes the carry into dhx only
 template <typename T>
 __global__ void __launch_bounds__(kThreads) gru_bwd_step_kernel(BwdArgs a, int t) {
-  __shared__ float red[kWaves][kRows][kSlice];
+  __shared__ float red[kWaves][1][kRows][kSlice];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int H = a.H, B = a.B, Tn = a.T;
   const int K = 3 * H;
@@ -220,9 +136,11 @@ __global__ void __launch_bounds__(kThreads) gru_bwd_step_kernel(BwdArgs a, int t
   const int mts = (nrows + 15) >> 4;
   const int s = t + 1;  // the step whose gradients arrive
 
-  f32x4 acc[kMT];
+  // the K loop of rnnstep.h's product for one tile, kept here as in lstm.hip:
+  // the shared one compiles to a slower loop for a single tile
+  f32x4 acc[kMT][1];
 #pragma unroll
-  for (int m = 0; m < kMT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int m = 0; m < kMT; ++m) acc[m][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (s < Tn) {
     const T* W = static_cast<const T*>(a.w_hhT);
     const int unit = j0 + (lane & 15);
@@ -237,19 +155,12 @@ __global__ void __launch_bounds__(kThreads) gru_bwd_step_kernel(BwdArgs a, int t
           const int row = b0 + m * 16 + (lane & 15);
           const typename MT<T>::frag af =
               row < B ? load_f8<T>(a.dgh + ((long long)row * Tn + s) * K, kk, K, a.vec_g) : MT<T>::zero();
-          MT<T>::mma(acc[m], af, bw);
+          MT<T>::mma(acc[m][0], af, bw);
         }
       }
     }
   }
-#pragma unroll
-  for (int m = 0; m < kMT; ++m) {
-    if (m < mts) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[w][m * 16 + 4 * (lane >> 4) + r][lane & 15] = acc[m][r];
-    }
-  }
-  __syncthreads();
+  meet<1>(red, acc, mts, lane, w);
 
   const long long BH = (long long)B * H;
   for (int e = tid; e < nrows * kSlice; e += kThreads) {
@@ -263,9 +174,7 @@ __global__ void __launch_bounds__(kThreads) gru_bwd_step_kernel(BwdArgs a, int t
     } else {
       const float dnext = a.dhw[(s & 1) * BH + bj];
       if (!a.lens || s < a.lens[b]) {
-        float mm = red[0][rr][jj];
-#pragma unroll
-        for (int ww = 1; ww < kWaves; ++ww) mm += red[ww][rr][jj];
+        const float mm = total<1>(red, 0, rr, jj);
         const float zn = a.save[((long long)b * Tn + s) * 4 * H + H + j];
         carry = zn * dnext + mm;
       } else {
@@ -285,7 +194,14 @@ __global__ void __launch_bounds__(kThreads) gru_bwd_step_kernel(BwdArgs a, int t
       const float* sv = a.save + bt * 4 * H + j;
       const float r = sv[0], z = sv[H], n = sv[2 * H], q = sv[3 * H];
       const float hp = t == 0 ? (a.hx ? a.hx[bj] : 0.f) : a.state[(bt - 1) * H + j];
-      dn = dh * (1.f - z) * (1.f - n * n);
+      // n * n is rounded before the subtraction: left to the compiler, whether
+      // 1 - n * n becomes one fma turned on how the code around it was written
+      float nn;
+      {
+#pragma clang fp contract(off)
+        nn = n * n;
+      }
+      dn = dh * (1.f - z) * (1.f - nn);
       dz = dh * (hp - n) * z * (1.f - z);
       dr = dn * q * r * (1.f - r);
       dnr = dn * r;
@@ -298,46 +214,6 @@ __global__ void __launch_bounds__(kThreads) gru_bwd_step_kernel(BwdArgs a, int t
     gh[0] = dr;
     gh[H] = dz;
     gh[2 * H] = dnr;
-  }
-}
-
-// out (N, D) = rows of the one-hot table of Embedding(consider_as_one_hot):
-// D = V - 1 columns, the blank row zero, ids above the blank shifted down
-__global__ void __launch_bounds__(kRowThreads)
-    embed_onehot_kernel(const int* __restrict__ ids, int blank, int D, float* __restrict__ out) {
-  const int v = ids[blockIdx.x];
-  const int idx = v == blank ? -1 : (v < blank ? v : v - 1);
-  float* o = out + (long long)blockIdx.x * D;
-  for (int d = threadIdx.x; d < D; d += kRowThreads) o[d] = d == idx ? 1.f : 0.f;
-}
-
-// out (N, D) = weight[ids] (an id outside [0, V) gives a zero row)
-__global__ void __launch_bounds__(kRowThreads)
-    embed_gather_kernel(const int* __restrict__ ids, const float* __restrict__ weight, int V, int D,
-                        float* __restrict__ out) {
-  const int v = ids[blockIdx.x];
-  const bool hit = v >= 0 && v < V;
-  float* o = out + (long long)blockIdx.x * D;
-  const float* wr = weight + (long long)(hit ? v : 0) * D;
-  for (int d = threadIdx.x; d < D; d += kRowThreads) o[d] = hit ? wr[d] : 0.f;
-}
-
-// grid ncodes: out[code] = sum of src rows order[offs[code] .. offs[code+1]),
-// added in list order (order: row ids stably sorted by code)
-__global__ void __launch_bounds__(kRowThreads)
-    segsum_rows_kernel(const float* __restrict__ src, const long long* __restrict__ order,
-                       const long long* __restrict__ offs, long long items, int D, float* __restrict__ out) {
-  const int code = blockIdx.x;
-  long long beg = offs[code], end = offs[code + 1];
-  beg = beg < 0 ? 0 : beg;
-  end = end > items ? items : end;
-  for (int d = threadIdx.x; d < D; d += kRowThreads) {
-    float s = 0.f;
-    for (long long i = beg; i < end; ++i) {
-      const long long it = order[i];
-      if (it >= 0 && it < items) s += src[it * D + d];
-    }
-    out[(long long)code * D + d] = s;
   }
 }
 
@@ -363,15 +239,7 @@ SBK_API int sbk_gru_fwd(int bf16, const void* w_hh, const float* b_hh, const flo
   a.blank = blank; a.I = I; a.B = B; a.T = T; a.H = H;
   a.vec_w = aligned16(w_hh) && H % (bf16 ? 8 : 4) == 0;
   a.vec_h = aligned16(state) && H % 4 == 0 && (!hx || aligned16(hx));
-  const dim3 grid((H + kSlice - 1) / kSlice, (B + kRows - 1) / kRows);
-  for (int t = 0; t < T; ++t) {
-    if (bf16)
-      hipLaunchKernelGGL(gru_fwd_step_kernel<bf16_t>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, t);
-    else
-      hipLaunchKernelGGL(gru_fwd_step_kernel<float>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, t);
-    SBK_CHECK_LAUNCH();
-  }
-  return 0;
+  return launch_steps(bf16 ? gru_fwd_step_kernel<bf16_t> : gru_fwd_step_kernel<float>, a, 1, 0, T, 1, stream);
 }
 
 // The backward steps t = T-1 .. 0 and the carry into dhx.  w_hhT = W_hh^T
@@ -390,42 +258,5 @@ SBK_API int sbk_gru_bwd(int bf16, const void* w_hhT, const float* hx, const floa
   a.B = B; a.T = T; a.H = H;
   a.vec_w = aligned16(w_hhT) && (3 * H) % (bf16 ? 8 : 4) == 0;
   a.vec_g = aligned16(dgh) && (3 * H) % 4 == 0;
-  const dim3 grid((H + kSlice - 1) / kSlice, (B + kRows - 1) / kRows);
-  for (int t = T - 1; t >= -1; --t) {
-    if (bf16)
-      hipLaunchKernelGGL(gru_bwd_step_kernel<bf16_t>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, t);
-    else
-      hipLaunchKernelGGL(gru_bwd_step_kernel<float>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, t);
-    SBK_CHECK_LAUNCH();
-  }
-  return 0;
-}
-
-// out (N, V - 1) fp32: the one-hot rows of ids (N) int32 with a zero row for `blank`.
-SBK_API int sbk_embed_onehot(const int* ids, int N, int V, int blank, float* out, void* stream) {
-  if (!ids || !out || N <= 0 || V <= 1 || blank < 0 || blank >= V) return SBK_ERR_ARG;
-  hipLaunchKernelGGL(embed_onehot_kernel, dim3(N), dim3(kRowThreads), 0, (hipStream_t)stream, ids, blank, V - 1, out);
-  SBK_CHECK_LAUNCH();
-  return 0;
-}
-
-// out (N, D) fp32 = weight (V, D)[ids (N) int32].
-SBK_API int sbk_embed_gather(const int* ids, const float* weight, int N, int V, int D, float* out, void* stream) {
-  if (!ids || !weight || !out || N <= 0 || V <= 0 || D <= 0) return SBK_ERR_ARG;
-  hipLaunchKernelGGL(embed_gather_kernel, dim3(N), dim3(kRowThreads), 0, (hipStream_t)stream, ids, weight, V, D, out);
-  SBK_CHECK_LAUNCH();
-  return 0;
-}
-
-// out (ncodes, D) fp32: per-code sums of the rows of src (items, D) fp32 over
-// order (items) int64 — row ids stably sorted by code — and offs (ncodes + 1)
-// int64, the start of every code's run.  Rows are added in list order: no
-// atomics, run-to-run identical.
-SBK_API int sbk_segsum_rows(const float* src, const long long* order, const long long* offs, long long items,
-                            int ncodes, int D, float* out, void* stream) {
-  if (!src || !order || !offs || !out || items <= 0 || ncodes <= 0 || D <= 0) return SBK_ERR_ARG;
-  hipLaunchKernelGGL(segsum_rows_kernel, dim3(ncodes), dim3(kRowThreads), 0, (hipStream_t)stream, src, order, offs, items,
-                     D, out);
-  SBK_CHECK_LAUNCH();
-  return 0;
+  return launch_steps(bf16 ? gru_bwd_step_kernel<bf16_t> : gru_bwd_step_kernel<float>, a, 1, T - 1, T + 1, -1, stream);
 }

@@ -5,84 +5,43 @@
 //   g = tanh(gi_g + W_hg h + b_hg)           o = sigmoid(gi_o + W_ho h + b_ho)
 //   c_t = f * c_{t-1} + i * g                h_t = o * tanh(c_t)
 //
-// The layout of gru.hip: one launch per time step, forward and backward; the
-// dependency between steps is stream order.  No persistent kernel, no grid
-// barrier, no flag between workgroups, no float atomics.  Both directions of
+// One launch per time step on the skeleton of rnnstep.h.  Both directions of
 // a bidirectional layer share a launch: grid (ceil(H / 16), ceil(B / 32), D),
 // launch s working on time s in direction 0 and T-1-s in direction 1, so a
 // bidirectional layer costs T launches forward and T+1 backward like a
 // unidirectional one.  sbk_lstm_fwd / sbk_lstm_bwd enqueue all launches of a
-// layer from the host side of the library.
+// layer.
 //
-// Forward step, 8 waves.  A workgroup owns 16 hidden units of one direction
-// for all four gates and up to 32 batch rows: the four 16-column tiles
-// W_hh[d][g * H + j0 .. j0 + 16, :] are MFMA B operands read from memory as
-// they are (8 consecutive K elements per lane), the rows of the previous h of
-// that direction are the A operand (fp32 state, rounded to bf16 in bf16 mode;
-// exact-fp32 MFMA in fp32 mode).  K is dealt to the eight waves in 32-element
-// chunks; their partial tiles meet in LDS — 4 gates x 8 waves x 32 rows x 16
-// units of fp32, the 64 KiB of a static allocation, two workgroups per CU —
-// and are added in wave order.  The epilogue adds the input pre-activations
-// (rows of the dense gi (B, T, D, 4H), or rows of the W_ih^T table gathered by
-// token id, the blank adding b_ih only), applies the gates and writes h_t and
-// c_t into hstate / cstate (B, T, D * H) at time t: nothing is updated in
-// place.  With lengths, a row with t >= len_b keeps (h, c) and its output row
-// is zero; in the reverse scan the row so carries (h0, c0) through its padding
-// and starts at t = len_b - 1.  When training, i, f, g, o are kept in save
-// (B, T, D, 4H); tanh(c_t) is recomputed in the backward from cstate.
+// Forward step.  A workgroup owns 16 hidden units of one direction for all
+// four gates: the product is the previous h of that direction against the
+// four 16-column tiles W_hh[d][g * H + j0 .. j0 + 16, :].  The partial tiles
+// take 4 gates x 8 waves x 32 rows x 16 units of fp32 in LDS, the 64 KiB of a
+// static allocation, two workgroups per CU.  The epilogue adds the input
+// pre-activations (rows of the dense gi (B, T, D, 4H), or rows of the W_ih^T
+// table gathered by token id, the blank adding b_ih only), applies the gates
+// and writes h_t and c_t into hstate / cstate (B, T, D * H) at time t:
+// nothing is updated in place.  With lengths, a row with t >= len_b keeps
+// (h, c) and its output row is zero; in the reverse scan the row so carries
+// (h0, c0) through its padding and starts at t = len_b - 1.  When training,
+// i, f, g, o are kept in save (B, T, D, 4H); tanh(c_t) is recomputed in the
+// backward from cstate.
 //
 // Backward step, same grid, order mirrored per direction; one more launch
 // gives the carry into dh0 / dc0.  With s the step whose gradients arrive
 // (t + 1 forward, t - 1 reverse):
-//   dh_t = dy_t + dG_s . W_hh[:, J]       (MFMA against W_hh^T, K = 4H dealt to the waves)
+//   dh_t = dy_t + dG_s . W_hh[:, J]       (the product against W_hh^T, K = 4H)
 //   dc_t = f_s * dc_s + dh_t * o_t * (1 - tanh^2 c_t)
 //   di = dc g i(1-i)   df = dc c_prev f(1-f)   dg = dc i (1-g^2)   do = dh tanh(c) o(1-o)
 // dG (B, T, D, 4H) is both the gradient of gi and the operand of the next
 // step's product.  A row masked at s passes dh and dc through; a row inactive
 // at t writes zero dG.  dh and dc ping-pong between the two halves of a
 // (2, 2, D, B, H) buffer.
-#include "mfma.h"
+#include "rnnstep.h"
 
 using namespace sbk;
+using namespace sbk::rnnstep;
 
 namespace {
-
-constexpr int kThreads = 512;
-constexpr int kWaves = 8;
-constexpr int kSlice = 16;  // hidden units of a workgroup: one MFMA tile
-constexpr int kRows = 32;   // batch rows of a workgroup
-constexpr int kMT = kRows / 16;
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// 8 elements row[k0 .. k0 + 8) of a K-element row as an MFMA fragment, zero
-// past K.  vec: the row start and K allow 16-byte reads.
-template <typename T>
-__device__ __forceinline__ typename MT<T>::frag load_w8(const T* row, int k0, int K, bool vec) {
-  if (vec && k0 + 8 <= K) return MT<T>::load(row + k0);
-  float v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = k0 + i < K ? MT<T>::to_f32(row[k0 + i]) : 0.f;
-  return MT<T>::from8(v);
-}
-
-// the same from an fp32 row, converted to T
-template <typename T>
-__device__ __forceinline__ typename MT<T>::frag load_f8(const float* row, int k0, int K, bool vec) {
-  float v[8];
-  if (vec && k0 + 8 <= K) {
-    const float4 a = *reinterpret_cast<const float4*>(row + k0);
-    const float4 b = *reinterpret_cast<const float4*>(row + k0 + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = k0 + i < K ? row[k0 + i] : 0.f;
-  }
-  return MT<T>::from8(v);
-}
-
-__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct FwdArgs {
   const void* w_hh;      // (D, 4H, H) in the compute dtype
@@ -120,46 +79,11 @@ __global__ void __launch_bounds__(kThreads) lstm_fwd_step_kernel(FwdArgs a, int 
   const long long offp = s == 0 ? (long long)d * B * H : tp * DH + (long long)d * H;
   const float* hprev = s == 0 ? (a.hx ? a.hx + offp : nullptr) : a.hstate + offp;
   const float* cprev = s == 0 ? (a.cx ? a.cx + offp : nullptr) : a.cstate + offp;
-  const bool vec_h = a.vec_h;
 
   f32x4 acc[kMT][4];
-#pragma unroll
-  for (int m = 0; m < kMT; ++m)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) acc[m][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (hprev) {
-    const T* W = static_cast<const T*>(a.w_hh) + (long long)d * 4 * H * H;
-    const int unit = j0 + (lane & 15);
-#pragma unroll 2
-    for (int k0 = w * 32; k0 < H; k0 += kWaves * 32) {
-      const int kk = k0 + 8 * (lane >> 4);
-      typename MT<T>::frag bw[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        bw[g] = unit < H ? load_w8<T>(W + ((long long)g * H + unit) * H, kk, H, a.vec_w) : MT<T>::zero();
-#pragma unroll
-      for (int m = 0; m < kMT; ++m) {
-        if (m < mts) {
-          const int row = b0 + m * 16 + (lane & 15);
-          const typename MT<T>::frag af =
-              row < B ? load_f8<T>(hprev + row * ldp, kk, H, vec_h) : MT<T>::zero();
-#pragma unroll
-          for (int g = 0; g < 4; ++g) MT<T>::mma(acc[m][g], af, bw[g]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < kMT; ++m) {
-    if (m < mts) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[w][g][m * 16 + 4 * (lane >> 4) + r][lane & 15] = acc[m][g][r];
-    }
-  }
-  __syncthreads();
+  product<T, 4>(acc, static_cast<const T*>(a.w_hh) + (long long)d * 4 * H * H, H, H, hprev, ldp, j0, b0, B, H, mts,
+                a.vec_w, a.vec_h, lane, w);
+  meet<4>(red, acc, mts, lane, w);
 
   const long long H4 = 4LL * H;
   for (int e = tid; e < nrows * kSlice; e += kThreads) {
@@ -170,14 +94,11 @@ __global__ void __launch_bounds__(kThreads) lstm_fwd_step_kernel(FwdArgs a, int 
     float pre[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float sum = red[0][g][rr][jj];
-#pragma unroll
-      for (int ww = 1; ww < kWaves; ++ww) sum += red[ww][g][rr][jj];
+      const float sum = total<4>(red, g, rr, jj);
       pre[g] = a.b_hh ? sum + a.b_hh[d * H4 + g * H + j] : sum;
     }
     if (a.tok) {
-      const int v = a.tok[bt];
-      const int idx = v == a.blank ? -1 : (v < a.blank ? v : v - 1);
+      const int idx = token_row(a.tok[bt], a.blank);
       const bool hit = idx >= 0 && idx < a.I;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -232,7 +153,7 @@ struct BwdArgs {
 // launch (time -1 / T) computes the carry into dhx, dcx only
 template <typename T>
 __global__ void __launch_bounds__(kThreads) lstm_bwd_step_kernel(BwdArgs a, int s) {
-  __shared__ float red[kWaves][kRows][kSlice];
+  __shared__ float red[kWaves][1][kRows][kSlice];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int H = a.H, B = a.B, Tn = a.T, D = a.D;
   const int K = 4 * H;
@@ -247,9 +168,11 @@ __global__ void __launch_bounds__(kThreads) lstm_bwd_step_kernel(BwdArgs a, int 
   const bool last = s == Tn;
   const long long DH = (long long)D * H;
 
-  f32x4 acc[kMT];
+  // the K loop of rnnstep.h's product for one tile, kept here: through the
+  // shared one a bf16 forward + backward call was 3-4 % slower
+  f32x4 acc[kMT][1];
 #pragma unroll
-  for (int m = 0; m < kMT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int m = 0; m < kMT; ++m) acc[m][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (arrives) {
     const T* W = static_cast<const T*>(a.w_hhT) + (long long)d * H * K;
     const int unit = j0 + (lane & 15);
@@ -265,19 +188,12 @@ __global__ void __launch_bounds__(kThreads) lstm_bwd_step_kernel(BwdArgs a, int 
           const typename MT<T>::frag af =
               row < B ? load_f8<T>(a.dG + (((long long)row * Tn + ts) * D + d) * K, kk, K, a.vec_g)
                       : MT<T>::zero();
-          MT<T>::mma(acc[m], af, bw);
+          MT<T>::mma(acc[m][0], af, bw);
         }
       }
     }
   }
-#pragma unroll
-  for (int m = 0; m < kMT; ++m) {
-    if (m < mts) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[w][m * 16 + 4 * (lane >> 4) + r][lane & 15] = acc[m][r];
-    }
-  }
-  __syncthreads();
+  meet<1>(red, acc, mts, lane, w);
 
   const long long BH = (long long)B * H;
   const long long half = 2 * D * BH;     // one parity of dw
@@ -294,10 +210,7 @@ __global__ void __launch_bounds__(kThreads) lstm_bwd_step_kernel(BwdArgs a, int 
       const float* src = a.dw + (ts & 1) * half + bj;
       const float dhs = src[0], dcs = src[D * BH];
       if (!a.lens || ts < a.lens[b]) {
-        float mm = red[0][rr][jj];
-#pragma unroll
-        for (int ww = 1; ww < kWaves; ++ww) mm += red[ww][rr][jj];
-        ch = mm;
+        ch = total<1>(red, 0, rr, jj);
         cc = a.save[(((long long)b * Tn + ts) * D + d) * K + H + j] * dcs;
       } else {
         ch = dhs;
@@ -362,15 +275,7 @@ SBK_API int sbk_lstm_fwd(int bf16, int D, const void* w_hh, const float* b_hh, c
   a.blank = blank; a.I = I; a.B = B; a.T = T; a.H = H; a.D = D;
   a.vec_w = aligned16(w_hh) && H % (bf16 ? 8 : 4) == 0;
   a.vec_h = aligned16(hstate) && H % 4 == 0 && (!hx || aligned16(hx));
-  const dim3 grid((H + kSlice - 1) / kSlice, (B + kRows - 1) / kRows, D);
-  for (int s = 0; s < T; ++s) {
-    if (bf16)
-      hipLaunchKernelGGL(lstm_fwd_step_kernel<bf16_t>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, s);
-    else
-      hipLaunchKernelGGL(lstm_fwd_step_kernel<float>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, s);
-    SBK_CHECK_LAUNCH();
-  }
-  return 0;
+  return launch_steps(bf16 ? lstm_fwd_step_kernel<bf16_t> : lstm_fwd_step_kernel<float>, a, D, 0, T, 1, stream);
 }
 
 // The T backward launches and the carry into (dhx, dcx).  w_hhT = W_hh^T per
@@ -391,13 +296,5 @@ SBK_API int sbk_lstm_bwd(int bf16, int D, const void* w_hhT, const float* cx, co
   // rows of 4H elements: 16-byte aligned in fp32, in bf16 for even H
   a.vec_w = aligned16(w_hhT) && (!bf16 || H % 2 == 0);
   a.vec_g = aligned16(dG);
-  const dim3 grid((H + kSlice - 1) / kSlice, (B + kRows - 1) / kRows, D);
-  for (int s = 0; s <= T; ++s) {
-    if (bf16)
-      hipLaunchKernelGGL(lstm_bwd_step_kernel<bf16_t>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, s);
-    else
-      hipLaunchKernelGGL(lstm_bwd_step_kernel<float>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, s);
-    SBK_CHECK_LAUNCH();
-  }
-  return 0;
+  return launch_steps(bf16 ? lstm_bwd_step_kernel<bf16_t> : lstm_bwd_step_kernel<float>, a, D, 0, T + 1, 1, stream);
 }

@@ -1,26 +1,29 @@
-"""Drop-ins for speechbrain.nnet.RNN.GRU (RNN.py:280-388) and LSTM
-(RNN.py:169-277) on HIP.  The GRU, the transducer recipes' prediction network
-`dec`, is described here; the LSTM (one or two directions, csrc/lstm.hip) by
-the docstring of its class below.
+"""Drop-ins for speechbrain.nnet.RNN.GRU (RNN.py:280-388), the transducer
+recipes' prediction network `dec`, and LSTM (RNN.py:169-277) on HIP.
 
-Same constructor, forward(x, hx=None, lengths=None) -> (output, hn) and
-state_dict keys (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0,
-rnn.bias_hh_l0, ..., torch's gate order r, z, n) as the reference, so its
-checkpoints load unchanged; `self.rnn` is a torch.nn.GRU used as the parameter
-container only (torch's init, then the reference's rnn_init), never called.
+Same constructor, forward(x, hx=None, lengths=None) -> (output, hn) — (hn, cn)
+for the LSTM, whose hx is a tuple (h0, c0) — and state_dict keys
+(rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, ..., the
+LSTM's second direction with `_reverse` suffixes; torch's gate order r, z, n /
+i, f, g, o) as the reference, so its checkpoints load unchanged; `self.rnn` is
+a torch.nn.GRU / torch.nn.LSTM used as the parameter container only (torch's
+init, then the reference's rnn_init), never called.
 
-What runs (csrc/gru.hip): the input projection of every layer is one MFMA GEMM
-over all time steps — or, for layer 0 fed by speechbrain_amd's one-hot
-Embedding, no GEMM at all: the step kernel gathers rows of a cached W_ih^T by
-token id.  The recurrence is one launch per time step with the gate math
-fused; the backward is one launch per step too, followed by the weight /
-input-gradient GEMMs of _autograd.  fp32 by default, bf16 operands (fp32
-state) under torch.autocast(bf16).
+What runs (csrc/gru.hip, csrc/lstm.hip on the skeleton of csrc/rnnstep.h):
+the input projection of every layer is one MFMA GEMM over all time steps, for
+both directions of an LSTM at once — or, for layer 0 fed by speechbrain_amd's
+one-hot Embedding, no GEMM at all: the step kernel gathers rows of a cached
+W_ih^T by token id.  The recurrence is one launch per time step with the gate
+math fused, both directions of an LSTM in the same launch (layers >= 1 read
+the 2H-wide output); the backward is one launch per step too, followed by the
+weight / input-gradient GEMMs of _autograd.  fp32 by default, bf16 operands
+(fp32 state) under torch.autocast(bf16).
 
 `lengths` are relative, as in the reference's pack_padded_sequence /
 pad_packed_sequence pair: row b runs int(lengths[b] * T) steps, its later
 outputs are zero, hn is its last valid state and the output is cut to the
-longest row.  Implemented as a per-row step mask inside the kernels.
+longest row.  Implemented as a per-row step mask inside the kernels, mirrored
+for the LSTM's reverse direction.
 
 The GRU is unidirectional only (`bidirectional=True` raises
 NotImplementedError); device tensors only (SbkError, no fallback).
@@ -49,6 +52,68 @@ def _rows_of_tokens(tok, blank, I):
     return torch.where(t == blank, torch.full_like(t, I), torch.where(t < blank, t, t - 1))
 
 
+def _steps(lengths, T):
+    """Steps per row, as torch's packing derives them from lengths * T."""
+    steps = (lengths * T).cpu().to(torch.int64)
+    if steps.dim() != 1 or int(steps.min()) < 1 or int(steps.max()) > T:
+        raise ValueError(f"lengths * T must lie in [1, {T}] (got {steps.tolist()})")
+    return steps
+
+
+def _input_preact(x, tok, w_ih, bih, dtype, cache, key):
+    """Input pre-activations of a layer for the stacked w_ih (each (G * H, I)):
+    the dense gi = x W_ih^T + bih of x (B, T, I), or, for one-hot token ids tok
+    (B, T), the table W_ih^T the step kernel gathers from.  Returns (gi, table,
+    xs, wk, B, T); xs (B * T, I) and the kernel copy wk serve the backward."""
+    bf = int(dtype == _bf16)
+    I = w_ih[0].shape[1]
+    gi = table = xs = wk = None
+    if tok is not None:
+        B, T = tok.shape
+        # the stacked W_ih transposed (I, D * G * H) fp32, holding the compute dtype's values
+        table = cache.get(key + "tab" + str(bf), w_ih, lambda: (
+            torch.cat([w.detach() for w in w_ih]).to(dtype).float().t().contiguous()))
+    else:
+        B, T = x.shape[:2]
+        vec = 8 if bf else 4
+        Kp = -(-I // vec) * vec
+        # K zero-padded to the GEMM's 16-byte vectors: one GEMM gives every direction's gi
+        wk = cache.get(key + "ih" + str(bf), w_ih, lambda: _enc.to_compute(
+            torch.nn.functional.pad(torch.cat([w.detach() for w in w_ih]), (0, Kp - I)), dtype))
+        xs = x.detach().reshape(B * T, I)
+        a = _enc.to_compute(xs, dtype)
+        if Kp != I:
+            a = torch.nn.functional.pad(a, (0, Kp - I))
+        gi = _enc.gemm(a, wk, bias=bih)
+    return gi, table, xs, wk, B, T
+
+
+def _input_grads(g2, tok, blank, I, xs, wk, dtype, xdt, B, T, want_w, want_x):
+    """(dW_ih stacked, dx) from g2 (B * T, D * G * H), the gradient of gi."""
+    dw_ih = dx = None
+    if tok is not None:
+        if want_w:
+            # per-token sum of the rows of g2: rows of d(W_ih^T); the blank has none
+            dw_ih = segsum_rows(g2, _rows_of_tokens(tok, blank, I), I).t().contiguous()
+    else:
+        if want_w:
+            # fp32 operands in both modes: with g2 and x both rounded to bf16 this
+            # gradient left the bf16 bound of tests/test_gpu_rnn.py (DESIGN.md)
+            dw_ih = A.wgrad(g2, xs.float())
+        if want_x:
+            dx = A.dgrad(A._as(g2, dtype), wk)[:, :I].reshape(B, T, I).to(xdt)
+    return dw_ih, dx
+
+
+def _hprev(state, h0, reverse=False):
+    """(B * T, H): the h every step of one direction started from; state
+    (B, T, H) carried, h0 (B, H) or None.  The reverse scan's carried padding
+    makes [state[:, 1:], h0] right for ragged rows."""
+    B, T, H = state.shape
+    first = h0.unsqueeze(1) if h0 is not None else torch.zeros(B, 1, H, device=state.device, dtype=_f32)
+    return torch.cat([state[:, 1:], first] if reverse else [first, state[:, :T - 1]], 1).reshape(B * T, H)
+
+
 class _GRULayerFn(torch.autograd.Function):
     """One GRU layer over a sequence.  x (B, T, I) or None with tok (B, T)
     int32 one-hot token ids; hx (B, H) or None; lens (B,) int32 or None."""
@@ -64,24 +129,7 @@ class _GRULayerFn(torch.autograd.Function):
         bih = None if b_ih is None else b_ih.detach()
         bhh = None if b_hh is None else b_hh.detach()
         hx0 = None if hx is None else hx.detach().float().contiguous()
-        a = wk = gi = table = xs = None
-        if tok is not None:
-            B, T = tok.shape
-            # W_ih^T (I, 3H) fp32, holding the compute dtype's values
-            table = cache.get(key + "tab" + str(bf), [w_ih], lambda: (
-                w_ih.detach().to(dtype).float().t().contiguous()))
-        else:
-            B, T = x.shape[:2]
-            vec = 8 if bf else 4
-            Kp = -(-I // vec) * vec
-            # kernel copy of W_ih, K zero-padded to the GEMM's 16-byte vectors
-            wk = cache.get(key + "ih" + str(bf), [w_ih], lambda: _enc.to_compute(
-                torch.nn.functional.pad(w_ih.detach(), (0, Kp - I)), dtype))
-            xs = x.detach().reshape(B * T, I)
-            a = _enc.to_compute(xs, dtype)
-            if Kp != I:
-                a = torch.nn.functional.pad(a, (0, Kp - I))
-            gi = _enc.gemm(a, wk, bias=bih)
+        gi, table, xs, wk, B, T = _input_preact(x, tok, [w_ih], bih, dtype, cache, key)
         state = torch.empty(B, T, H, device=dev, dtype=_f32)
         y = state if lens is None else torch.empty(B, T, H, device=dev, dtype=_f32)
         save = torch.empty(B, T, 4, H, device=dev, dtype=_f32) if need else None
@@ -112,97 +160,16 @@ class _GRULayerFn(torch.autograd.Function):
         check(lib().sbk_gru_bwd(bf, ptr(whhT), ptr(hx0), ptr(state), ptr(save), ptr(dy), ptr(dhn), ptr(lens), B, T, H,
                                 ptr(dgi), ptr(dgh), ptr(dhw), ptr(dhx), stream_of(state)), "sbk_gru_bwd")
         gi2, gh2 = dgi.view(B * T, 3 * H), dgh.view(B * T, 3 * H)
-        first = hx0.unsqueeze(1) if hx0 is not None else torch.zeros(B, 1, H, device=dev, dtype=_f32)
-        hprev = torch.cat([first, state[:, :T - 1]], 1).reshape(B * T, H)
         need = ctx.needs_input_grad
-        dx = dw_ih = dw_hh = db_ih = db_hh = None
+        dw_hh = db_ih = db_hh = None
         if need[4]:
-            dw_hh = A.wgrad(A._as(gh2, dtype), A._as(hprev, dtype))
-        if tok is not None:
-            if need[3]:
-                # per-token sum of the dgi rows: rows of d(W_ih^T); the blank has none
-                dw_ih = segsum_rows(gi2, _rows_of_tokens(tok, blank, I), I).t().contiguous()
-        else:
-            if need[3]:
-                # fp32 operands in both modes: with dgi and x both rounded to bf16 this
-                # gradient left the bf16 bound of tests/test_gpu_rnn.py
-                dw_ih = A.wgrad(gi2, xs.float())
-            if need[0]:
-                dx = A.dgrad(A._as(gi2, dtype), wk)[:, :I].reshape(B, T, I).to(xdt)
+            dw_hh = A.wgrad(A._as(gh2, dtype), A._as(_hprev(state, hx0), dtype))
+        dw_ih, dx = _input_grads(gi2, tok, blank, I, xs, wk, dtype, xdt, B, T, need[3], need[0])
         if has_bih and need[5]:
             db_ih = A.rowsum(gi2)
         if has_bhh and need[6]:
             db_hh = A.rowsum(gh2)
         return dx, None, None, dw_ih, dw_hh, db_ih, db_hh, (dhx if has_hx and need[7] else None), None, None, None, None
-
-
-class GRU(torch.nn.Module):
-    def __init__(self, hidden_size, input_shape=None, input_size=None, num_layers=1, bias=True, dropout=0.0,
-                 re_init=True, bidirectional=False):
-        super().__init__()
-        self.reshape = False
-        if input_shape is None and input_size is None:
-            raise ValueError("Expected one of input_shape or input_size.")
-        if bidirectional:
-            raise NotImplementedError("speechbrain_amd GRU is unidirectional (the transducer prediction network); "
-                                      "bidirectional=True has no kernel")
-        if input_size is None:
-            if len(input_shape) > 3:
-                self.reshape = True
-            input_size = torch.prod(torch.tensor(input_shape[2:])).item()
-        # parameter container: torch's names and init; its forward is never called
-        self.rnn = torch.nn.GRU(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
-                                dropout=dropout, bidirectional=False, bias=bias, batch_first=True)
-        if re_init:
-            rnn_init(self.rnn)
-        self._wc = _enc.WeightCache()
-
-    @staticmethod
-    def _steps(lengths, T):
-        """Steps per row, as torch's packing derives them from lengths * T."""
-        steps = (lengths * T).cpu().to(torch.int64)
-        if steps.dim() != 1 or int(steps.min()) < 1 or int(steps.max()) > T:
-            raise ValueError(f"lengths * T must lie in [1, {T}] (got {steps.tolist()})")
-        return steps
-
-    def forward(self, x, hx=None, lengths=None):
-        if self.reshape and x.ndim == 4:
-            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
-        rnn = self.rnn
-        require_device(x, hx, rnn.weight_hh_l0)
-        if x.ndim != 3 or x.shape[-1] != rnn.input_size:
-            raise ValueError(f"GRU expects (batch, time, {rnn.input_size}) (got {tuple(x.shape)})")
-        B, T, _ = x.shape
-        L, H = rnn.num_layers, rnn.hidden_size
-        if hx is not None and tuple(hx.shape) != (L, B, H):
-            raise ValueError(f"hx must be {(L, B, H)} (got {tuple(hx.shape)})")
-        tag = getattr(x, "_sbk_onehot", None)
-        tok = blank = None
-        if tag is not None and tag[2] == x._version and tuple(tag[0].shape) == (B, T):
-            tok, blank = tag[0], tag[1]   # unmodified one-hot rows: layer 0 never reads x
-        lens = None
-        if lengths is not None:
-            steps = self._steps(lengths, T)
-            Tn = int(steps.max())
-            if Tn < T:
-                x = x[:, :Tn]
-                tok = None if tok is None else tok[:, :Tn].contiguous()
-                T = Tn
-            if int(steps.min()) < T:
-                lens = steps.to(device=x.device, dtype=torch.int32)
-        dtype = _enc.compute_dtype()
-        y, hns = x, []
-        for layer in range(L):
-            w = [getattr(rnn, f"{n}_l{layer}", None) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-            h0 = None if hx is None else hx[layer]
-            if layer == 0 and tok is not None:
-                y, hn = _GRULayerFn.apply(None, tok, blank, *w, h0, lens, dtype, self._wc, f"l{layer}")
-            else:
-                y, hn = _GRULayerFn.apply(y, None, 0, *w, h0, lens, dtype, self._wc, f"l{layer}")
-            hns.append(hn)
-            if layer < L - 1 and rnn.dropout > 0:
-                y = A.dropout(y, rnn.dropout, self.training)
-        return y, torch.stack(hns, 0)
 
 
 class _LSTMLayerFn(torch.autograd.Function):
@@ -228,24 +195,7 @@ class _LSTMLayerFn(torch.autograd.Function):
         bhh = None if b_hh[0] is None else torch.cat([b.detach() for b in b_hh])
         hx0 = None if h0 is None else h0.detach().float().contiguous()
         cx0 = None if c0 is None else c0.detach().float().contiguous()
-        a = wk = gi = table = xs = None
-        if tok is not None:
-            B, T = tok.shape
-            # the stacked W_ih transposed (I, D * 4H) fp32, holding the compute dtype's values
-            table = cache.get(key + "tab" + str(bf), w_ih, lambda: (
-                torch.cat([w.detach() for w in w_ih]).to(dtype).float().t().contiguous()))
-        else:
-            B, T = x.shape[:2]
-            vec = 8 if bf else 4
-            Kp = -(-I // vec) * vec
-            # K zero-padded to the GEMM's 16-byte vectors: one GEMM gives both directions' gi
-            wk = cache.get(key + "ih" + str(bf), w_ih, lambda: _enc.to_compute(
-                torch.nn.functional.pad(torch.cat([w.detach() for w in w_ih]), (0, Kp - I)), dtype))
-            xs = x.detach().reshape(B * T, I)
-            a = _enc.to_compute(xs, dtype)
-            if Kp != I:
-                a = torch.nn.functional.pad(a, (0, Kp - I))
-            gi = _enc.gemm(a, wk, bias=bih)
+        gi, table, xs, wk, B, T = _input_preact(x, tok, w_ih, bih, dtype, cache, key)
         hstate = torch.empty(B, T, D * H, device=dev, dtype=_f32)
         cstate = torch.empty(B, T, D * H, device=dev, dtype=_f32)
         y = hstate if lens is None else torch.empty(B, T, D * H, device=dev, dtype=_f32)
@@ -287,27 +237,13 @@ class _LSTMLayerFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         nw = 10                      # position of the first weight among forward's inputs
         grads = [None] * (4 * D)
-        dx = None
         for d in range(D):
             if need[nw + 4 * d + 1]:
-                first = hx0[d].unsqueeze(1) if hx0 is not None else torch.zeros(B, 1, H, device=dev, dtype=_f32)
-                hd = hstate[:, :, d * H:(d + 1) * H]
-                # the h each step started from: the reverse scan's carried padding makes
-                # [state[:, 1:], h0] right for ragged rows
-                hprev = torch.cat([first, hd[:, :T - 1]] if d == 0 else [hd[:, 1:], first], 1).reshape(B * T, H)
+                hprev = _hprev(hstate[:, :, d * H:(d + 1) * H], None if hx0 is None else hx0[d], reverse=d == 1)
                 gd = dG[:, :, d].reshape(B * T, 4 * H)
                 grads[4 * d + 1] = A.wgrad(A._as(gd, dtype), A._as(hprev, dtype))
         want_ih = any(need[nw + 4 * d] for d in range(D))
-        if tok is not None:
-            if want_ih:
-                # per-token sum of the dG rows: rows of d(W_ih^T); the blank has none
-                dw_ih = segsum_rows(g2, _rows_of_tokens(tok, blank, I), I).t().contiguous()
-        else:
-            if want_ih:
-                # fp32 operands in both modes, as in the GRU
-                dw_ih = A.wgrad(g2, xs.float())
-            if need[0]:
-                dx = A.dgrad(A._as(g2, dtype), wk)[:, :I].reshape(B, T, I).to(xdt)
+        dw_ih, dx = _input_grads(g2, tok, blank, I, xs, wk, dtype, xdt, B, T, want_ih, need[0])
         if want_ih:
             for d in range(D):
                 grads[4 * d] = dw_ih[d * 4 * H:(d + 1) * 4 * H]
@@ -322,18 +258,11 @@ class _LSTMLayerFn(torch.autograd.Function):
                 None, None, None, None, None, *grads)
 
 
-class LSTM(torch.nn.Module):
-    """Drop-in for speechbrain.nnet.RNN.LSTM (RNN.py:169-277) on HIP
-    (csrc/lstm.hip): forward(x, hx=None, lengths=None) -> (output, (hn, cn)),
-    one or two directions, torch's state_dict keys (`_reverse` suffixes) and
-    gate order i, f, g, o.  `self.rnn` is a torch.nn.LSTM used as the parameter
-    container only.  Per layer: one MFMA GEMM gives both directions' input
-    pre-activations (or none, for a tagged one-hot Embedding input to layer 0),
-    then one launch per time step runs both directions' recurrence; layers
-    >= 1 read the 2H-wide output.  fp32 by default, bf16 operands with fp32
-    (h, c) state under torch.autocast(bf16).  `lengths` as in the GRU: a
-    per-row step mask, mirrored for the reverse direction, which reproduces
-    torch's packed sequences.  Device tensors only (SbkError, no fallback)."""
+class _Recurrent(torch.nn.Module):
+    """The constructor and the forward preamble of both cells."""
+
+    _cell = None            # torch.nn.GRU / torch.nn.LSTM: the parameter container
+    _one_way = None         # why bidirectional=True is refused, where it has no kernel
 
     def __init__(self, hidden_size, input_shape=None, input_size=None, num_layers=1, bias=True, dropout=0.0,
                  re_init=True, bidirectional=False):
@@ -341,42 +270,37 @@ class LSTM(torch.nn.Module):
         self.reshape = False
         if input_shape is None and input_size is None:
             raise ValueError("Expected one of input_shape or input_size.")
+        if bidirectional and self._one_way:
+            raise NotImplementedError(self._one_way)
         if input_size is None:
             if len(input_shape) > 3:
                 self.reshape = True
             input_size = torch.prod(torch.tensor(input_shape[2:])).item()
         # parameter container: torch's names and init; its forward is never called
-        self.rnn = torch.nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
-                                 dropout=dropout, bidirectional=bidirectional, bias=bias, batch_first=True)
+        self.rnn = self._cell(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
+                              dropout=dropout, bidirectional=bidirectional, bias=bias, batch_first=True)
         if re_init:
             rnn_init(self.rnn)
         self._wc = _enc.WeightCache()
 
-    _steps = staticmethod(GRU._steps)
-
-    def forward(self, x, hx=None, lengths=None):
+    def _prepare(self, x, lengths):
+        """x as (batch, time, input_size), cut to the longest row; the token
+        ids tok (B, T) and blank of an unmodified one-hot Embedding output (or
+        None, None); lens (B,) int32 steps per row when the rows are ragged
+        (or None).  Returns (x, tok, blank, lens, T)."""
         if self.reshape and x.ndim == 4:
             x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
-        rnn = self.rnn
-        if hx is not None and not (isinstance(hx, (tuple, list)) and len(hx) == 2):
-            raise ValueError("hx must be a tuple (h0, c0)")
-        h0, c0 = (None, None) if hx is None else hx
-        if x.ndim != 3 or x.shape[-1] != rnn.input_size:
-            raise ValueError(f"LSTM expects (batch, time, {rnn.input_size}) (got {tuple(x.shape)})")
+        if x.ndim != 3 or x.shape[-1] != self.rnn.input_size:
+            raise ValueError(f"{self._cell.__name__} expects (batch, time, {self.rnn.input_size}) "
+                             f"(got {tuple(x.shape)})")
         B, T, _ = x.shape
-        L, H, D = rnn.num_layers, rnn.hidden_size, 2 if rnn.bidirectional else 1
-        for s in (h0, c0):
-            if hx is not None and (not torch.is_tensor(s) or tuple(s.shape) != (L * D, B, H)):
-                raise ValueError(f"hx must be two tensors of {(L * D, B, H)} "
-                                 f"(got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__})")
-        require_device(x, h0, c0, rnn.weight_hh_l0)
         tag = getattr(x, "_sbk_onehot", None)
         tok = blank = None
         if tag is not None and tag[2] == x._version and tuple(tag[0].shape) == (B, T):
             tok, blank = tag[0], tag[1]   # unmodified one-hot rows: layer 0 never reads x
         lens = None
         if lengths is not None:
-            steps = self._steps(lengths, T)
+            steps = _steps(lengths, T)
             Tn = int(steps.max())
             if Tn < T:
                 x = x[:, :Tn]
@@ -384,6 +308,51 @@ class LSTM(torch.nn.Module):
                 T = Tn
             if int(steps.min()) < T:
                 lens = steps.to(device=x.device, dtype=torch.int32)
+        return x, tok, blank, lens, T
+
+
+class GRU(_Recurrent):
+    _cell = torch.nn.GRU
+    _one_way = ("speechbrain_amd GRU is unidirectional (the transducer prediction network); "
+                "bidirectional=True has no kernel")
+
+    def forward(self, x, hx=None, lengths=None):
+        rnn = self.rnn
+        require_device(x, hx, rnn.weight_hh_l0)
+        x, tok, blank, lens, T = self._prepare(x, lengths)
+        B, L, H = x.shape[0], rnn.num_layers, rnn.hidden_size
+        if hx is not None and tuple(hx.shape) != (L, B, H):
+            raise ValueError(f"hx must be {(L, B, H)} (got {tuple(hx.shape)})")
+        dtype = _enc.compute_dtype()
+        y, hns = x, []
+        for layer in range(L):
+            w = [getattr(rnn, f"{n}_l{layer}", None) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+            h0 = None if hx is None else hx[layer]
+            if layer == 0 and tok is not None:
+                y, hn = _GRULayerFn.apply(None, tok, blank, *w, h0, lens, dtype, self._wc, f"l{layer}")
+            else:
+                y, hn = _GRULayerFn.apply(y, None, 0, *w, h0, lens, dtype, self._wc, f"l{layer}")
+            hns.append(hn)
+            if layer < L - 1 and rnn.dropout > 0:
+                y = A.dropout(y, rnn.dropout, self.training)
+        return y, torch.stack(hns, 0)
+
+
+class LSTM(_Recurrent):
+    _cell = torch.nn.LSTM
+
+    def forward(self, x, hx=None, lengths=None):
+        rnn = self.rnn
+        if hx is not None and not (isinstance(hx, (tuple, list)) and len(hx) == 2):
+            raise ValueError("hx must be a tuple (h0, c0)")
+        h0, c0 = (None, None) if hx is None else hx
+        x, tok, blank, lens, T = self._prepare(x, lengths)
+        B, L, H, D = x.shape[0], rnn.num_layers, rnn.hidden_size, 2 if rnn.bidirectional else 1
+        for s in (h0, c0):
+            if hx is not None and (not torch.is_tensor(s) or tuple(s.shape) != (L * D, B, H)):
+                raise ValueError(f"hx must be two tensors of {(L * D, B, H)} "
+                                 f"(got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__})")
+        require_device(x, h0, c0, rnn.weight_hh_l0)
         dtype = _enc.compute_dtype()
         y, hns, cns = x, [], []
         for layer in range(L):
