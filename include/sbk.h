@@ -327,6 +327,20 @@ int sbk_ffn_chain(const float* x, int M, int D, int d_eff, int H, int act, float
                   float alphab, float* out, const float* gn, const float* bn, float epsn, void* u, int u_bf16,
                   const void* img, long long img_elems, int np, void* yp, void* stream);
 
+/* Tile owned by launch index orig of nwg workgroups in the XCD-contiguous
+ * order (sbk_conv_ffn_chain / sbk_conv_ffn_tail, the GEMMs, attention):
+ * blocks of one orig % 8 own one contiguous run of tiles, the runs ascending
+ * with the residue.  A bijection of [0, nwg); -1 outside it.  Host only. */
+int sbk_xcd_tile(int nwg, int orig);
+
+/* The out_proj weight wo (D, D) bf16 as the conv stage of sbk_conv_ffn_chain /
+ * sbk_conv_ffn_tail streams it: 4 tiles of 256 rows x 64 k, rows swizzled as
+ * in sbk_ffn_image (as many elements as wo).  Those two entry points take
+ * this image as their `wo` argument; sbk_conv_module_pre takes wo itself.
+ * D = 256; img must not alias wo. */
+long long sbk_wo_image_elems(int D);
+int sbk_wo_image(const void* wo, int D, void* img, void* stream);
+
 /* Weight-stream image of the convolution-module stage of sbk_conv_ffn_chain:
  * w1p (2D, D) GLU-permuted and w2 (D, D) bf16 as 12 tiles of 256 rows x 64 k
  * in stream order (8 of w1p: per 64 k, the first then the second GLU group of
@@ -338,8 +352,8 @@ int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, void* stre
  * projection tail (np > 0) in one launch, one workgroup per 48-frame tile of
  * one utterance: the convolution module's output rows stay on the CU as the
  * chain's input and residual.  c* arguments: the convolution module's (as
- * sbk_conv_module_pre; cimg = sbk_conv_image(w1p, w2)); H .. yp: the chain's
- * (as sbk_ffn_chain).  out (B*T, D) fp32 receives block B's output and must
+ * sbk_conv_module_pre, except that wo is sbk_wo_image(wo), not wo itself;
+ * cimg = sbk_conv_image(w1p, w2)); H .. yp: the chain's (as sbk_ffn_chain).  out (B*T, D) fp32 receives block B's output and must
  * not alias x; yp (B*T, np) bf16.  D = 256, K <= 31. */
 int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D, int d_eff,
                        const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg, long long cimg_elems,

@@ -372,6 +372,28 @@ def conv_image(w1p, w2):
     return _CONV_IMAGES.get((w1p, w2), 0, torch.cuda.current_stream(w1p.device), build=_build_conv_image)
 
 
+_WO_IMAGES = _ImageCache()
+
+
+def _build_wo_image(ws, np_, stream):
+    (wo,) = ws
+    D = wo.shape[0]
+    n = int(lib().sbk_wo_image_elems(D))
+    if n <= 0 or tuple(wo.shape) != (D, D):
+        raise SbkError(f"sbk_wo_image: unsupported shape {tuple(wo.shape)}")
+    img = torch.empty(n, device=wo.device, dtype=_bf16)
+    check(lib().sbk_wo_image(ptr(wo), D, ptr(img), ctypes.c_void_p(stream.cuda_stream)), "sbk_wo_image")
+    return img
+
+
+def wo_image(wo):
+    """The out_proj weight wo (D, D) bf16 as the conv stage of conv_ffn_chain /
+    conv_ffn_tail streams it; cached per tensor (and version) as the other images."""
+    if wo.dtype != _bf16 or not wo.is_contiguous():
+        raise TypeError("wo_image: a contiguous bf16 weight")
+    return _WO_IMAGES.get((wo,), 0, torch.cuda.current_stream(wo.device), build=_build_wo_image)
+
+
 @custom_op("sbk::ffn", mutates_args=())
 def _ffn_op(x: torch.Tensor, g0: torch.Tensor, b0: torch.Tensor, e0: float, w1: torch.Tensor, b1: torch.Tensor,
             act: int, slope: float, w2: torch.Tensor, b2: torch.Tensor, alpha: float, gp: Optional[torch.Tensor],
@@ -592,8 +614,9 @@ def _conv_ffn_chain_into(out, y, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc
     D = x.shape[1]
     H, NP = w1.shape[0], wp.shape[0]
     cimg = conv_image(w1p, cw2)
+    woimg = wo_image(wo)
     img = ffn_image(w1, w2, w1b, w2b, wp)
-    rc = lib().sbk_conv_ffn_chain(ptr(x), ptr(o), ptr(wo), ptr(bo), B, T, D, deff, ptr(cg0), ptr(cb0), float(ce0),
+    rc = lib().sbk_conv_ffn_chain(ptr(x), ptr(o), ptr(woimg), ptr(bo), B, T, D, deff, ptr(cg0), ptr(cb0), float(ce0),
                                   ptr(cimg), cimg.numel(), ptr(b1p), ptr(wc), ptr(bc), wc.shape[0], int(causal),
                                   ptr(cg1), ptr(cb1), float(ce1), ptr(cb2), ptr(kpm), H, act, float(slope), ptr(g0),
                                   ptr(b0), float(e0), ptr(b1), ptr(b2), float(alpha), ptr(gp), ptr(bp), float(ep),
@@ -655,8 +678,9 @@ def _conv_ffn_tail_into(u, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, 
                         act, slope, g0, b0, e0, w1, b1, w2, b2, alpha, gp, bp, ep, gn, bn, en, deff):
     """The launch of sbk::conv_ffn_tail into caller-owned u (>= B*T rows of D fp32)."""
     cimg = conv_image(w1p, cw2)
+    woimg = wo_image(wo)
     img = ffn_image(w1, w2)
-    rc = lib().sbk_conv_ffn_tail(ptr(x), ptr(o), ptr(wo), ptr(bo), B, T, x.shape[1], deff, ptr(cg0), ptr(cb0),
+    rc = lib().sbk_conv_ffn_tail(ptr(x), ptr(o), ptr(woimg), ptr(bo), B, T, x.shape[1], deff, ptr(cg0), ptr(cb0),
                                  float(ce0), ptr(cimg), cimg.numel(), ptr(b1p), ptr(wc), ptr(bc), wc.shape[0],
                                  int(causal), ptr(cg1), ptr(cb1), float(ce1), ptr(cb2), ptr(kpm), w1.shape[0], act,
                                  float(slope), ptr(g0), ptr(b0), float(e0), ptr(b1), ptr(b2), float(alpha), ptr(gp),

@@ -380,9 +380,7 @@ __global__ void __launch_bounds__(256) roll4_kernel(float* __restrict__ x, int N
   // XCD-aware bijective remap (workgroup i runs on XCD i % 8): the slabs of
   // an utterance — J * 16 B of every 128-B row line — go to one XCD, whose L2
   // then fetches each line once
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int slab = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int slab = sbk::xcd_tile(gridDim.x, blockIdx.x);
   const int n = slab / nslab, j0 = (slab - n * nslab) * J;
   if ((int)threadIdx.x < 2 * n_tmask) tms[threadIdx.x] = tmask[2 * n * n_tmask + threadIdx.x];
   const int RP = 256 / J;               // rows per pass

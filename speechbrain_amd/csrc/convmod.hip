@@ -183,9 +183,13 @@ __global__ void __launch_bounds__(CM_NT) conv_module_kernel(ConvModArgs a) {
   const int fr = lane & 15, g = lane >> 4, fk = 8 * g;
   const int fks = fk ^ cm_sw(fr);  // fk in the swizzled U / G rows mt*16 + fr
   const int nblk = (a.T + CM_BM - 1) / CM_BM;
-  // (an XCD-aware remap that put an utterance's consecutive tiles — which
-  // share halo rows — on one XCD measured equal: 30.4-30.5 vs 30.4-30.8 us,
-  // profiles/r04m_conv_xcd.log)
+  // launch order.  (An XCD-aware remap that put an utterance's consecutive
+  // tiles — which share halo rows — on one XCD measured equal here, 30.4-30.5
+  // vs 30.4-30.8 us, profiles/r04m_conv_xcd.log: this kernel alone in a loop
+  // over the same inputs, its start then latency-bound behind two
+  // s_waitcnt vmcnt(0), no traffic counters taken.  The fused conv-stage
+  // launches inside the step are another regime and carry sbk::xcd_tile,
+  // ffn.hip round 12; this kernel is not in the step and keeps its order.)
   const int tile = blockIdx.x;
   const int b = tile / nblk, t0 = (tile % nblk) * CM_BM;
   const int f0 = t0 - a.padL;  // frame of staged row 0

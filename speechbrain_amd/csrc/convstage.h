@@ -8,9 +8,9 @@
 // the chain's residual layout — wave w, lane (g, fr): rows mt*16 + fr, units
 // (w*2 + j)*16 + 4g + e — and never leave the CU.
 //   phase -1: wave w owns 32 out_proj units (two 16-unit tiles) of the 80
-//             staged frames; wo fragments straight from global (L2), o first
-//             across the workgroup, the second half of wo and all of x
-//             issued behind the MFMAs of the K-steps;
+//             staged frames; o first across the workgroup, wo as four
+//             image tiles through a 2-slot ring (LDS-DMA, as phases 1 and
+//             3), x behind the last tile;
 //   phase 1 : wave w owns GLU groups 2w and 2w + 1 (64 permuted rows of
 //             W1p): the U fragments of a K-step are read once per 64 weight
 //             rows instead of once per 32;
@@ -22,6 +22,22 @@
 // W2, 256 rows x 64 k each, ffn_image_kernel's row swizzle), a wave's share of
 // a tile one contiguous 4 KB run, through a 2-slot ring (one tile in flight
 // behind the one being read) in the buffers the phase does not use.
+// Round 12: phase -1 streams wo the same way (sbk_wo_image: 4 tiles; slots in
+// Us and the front of Cv, both free until LN0 writes U).  Before, its
+// fragments came from L2 16 rows x 64 B per wave instruction into 64 VGPRs
+// that were only a staging area, K-step by K-step, with x trickled in
+// between.  Now the queue holds, in order: o and the parameter rows (every
+// wave's, by a bare s_barrier), tiles 0 and 1, tile 2 once tile 0's fragments
+// are read, tile 3 and then all of x once tile 1's are.  The compiler does
+// not count asm LDS-DMA, so every load here is asm with a counted wait.
+// What it still adds: the chain's own parameter loads in front of this stage
+// are visible ones, and their first use (stage()) draws s_waitcnt vmcnt(0),
+// which also waits for tiles 0 and 1, in flight right behind o.  Timeline of
+// workgroup 128 (probe builds, cycles): o landed 5.2k -> 3.7k, last out_proj
+// MFMA 14.1k -> 12.0k, x landed 15.9k -> 13.1k, out_proj + sums done 18.0k ->
+// 15.2k with the XCD-contiguous tile order of ffn.hip round 12.  The K loop
+// is still 5.6k cycles for 80 MFMAs per wave: ~1.4k per tile, one tile's
+// fetch latency, since a 2-slot ring has one tile in flight.
 #pragma once
 
 struct ConvStageArgs {
@@ -38,7 +54,7 @@ struct ConvStageArgs {
   const float* b2;      // (D) or null
   const uint8_t* kpm;   // (B*T) padding mask or null
   const bf16_t* o;      // (B*T, D) attention output
-  const bf16_t* wo;     // (D, D) out_proj weight (row-major)
+  const bf16_t* wo;     // sbk_wo_image of the (D, D) out_proj weight
   const float* bo;      // (D) or null
 };
 
@@ -49,13 +65,7 @@ constexpr int CS_NW = FFN_NW, CS_NT = FFN_NT;
 constexpr int CS_S = CS_D + FFN_PAD;  // U / G row stride: rows swizzled by ffn_sw, as Xn / Hs
 constexpr int CS_TILE = 256 * 64;     // elements of an image tile
 constexpr int CS_P1T = 8, CS_P3T = 4; // image tiles of phase 1 (4 K-steps x 2 group halves) and phase 3
-// out_proj K-steps (of 8) whose wo fragments are issued before o is staged.
-// Same-box A/B of the step (ms): 1 1.0928, 2 1.0909, 4 1.0882, 8 1.0980
-// against 1.1075; a probe build may override it
-#ifndef CS_WO_AHEAD
-#define CS_WO_AHEAD 4
-#endif
-static_assert(CS_WO_AHEAD >= 1 && CS_WO_AHEAD <= CS_D / 32, "K-steps of out_proj");
+constexpr int CS_WOT = CS_D / 64;     // image tiles of the out_proj weight (sbk_wo_image)
 // LDS (bytes): U/V, G, the fp32 conv tile; ring slot 0 over G, slot 1 over the conv tile's front
 constexpr int CS_OFF_G = CS_ROWS * CS_S * 2, CS_OFF_CV = 2 * CS_OFF_G;
 constexpr int CS_LDS = CS_OFF_CV + CS_BM * CS_D * 4;
@@ -85,6 +95,13 @@ __device__ __forceinline__ void cs_issue(const bf16_t* img, int tile, bf16_t* sl
 // fragment of slot row `row`, 16-B chunk c (8 consecutive k)
 __device__ __forceinline__ bf16x8 cs_frag(const bf16_t* slot, int row, int c) {
   return *reinterpret_cast<const bf16x8*>(slot + row * 64 + ((c ^ ((row >> 1) & 7)) << 3));
+}
+// 16 B of bf16 by a load the compiler cannot see (the caller waits by count)
+typedef unsigned int cs_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ cs_u4 cs_gld16(const bf16_t* p) {
+  cs_u4 v;
+  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
 }
 __device__ __forceinline__ int cs_gldu8(const uint8_t* p) {
   int v;
@@ -136,69 +153,64 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
   {
     constexpr int OC = CS_ROWS * (CS_D / 8) / CS_NT;  // 16-B o chunks per thread
     static_assert(OC * CS_NT == CS_ROWS * (CS_D / 8), "whole chunks");
-    uint4 ov[OC];
+    // Every load of this phase is asm with a counted wait of its own: wo
+    // streams through a ring by asm LDS-DMA, which the compiler does not count,
+    // so its waits for visible loads in flight beside the tiles would drain them
+    cs_u4 ov[OC];
 #pragma unroll
     for (int i = 0; i < OC; ++i) {
       const int c = tid + i * CS_NT;
       const int r = c / (CS_D / 8), ch = c - r * (CS_D / 8);
       const int fc = min(max(f0 + r, 0), a.T - 1);
-      ov[i] = *reinterpret_cast<const uint4*>(a.o + (ubase + fc) * CS_D + ch * 8);
+      ov[i] = cs_gld16(a.o + (ubase + fc) * CS_D + ch * 8);
     }
     // LN0's scratch (partials, statistics, affine) sits past ring slot 1
     float* lnscr = Cv + CS_TILE / 2;
     constexpr int RS = CS_NW + 4;  // partial-row stride (floats), 16-B aligned
     static_assert(CS_TILE / 2 + 2 * CS_ROWS * RS + 2 * CS_ROWS + 2 * CS_D <= CS_BM * CS_D, "LN0 scratch fits");
     float* gb0s = lnscr + 2 * CS_ROWS * RS + 2 * CS_ROWS;  // [g0 | b0]
-    // unconditional, as bo below (threads CS_D / 2.. read b0 again and drop it):
-    // a load under a branch is merged with its zero by a register copy, and
-    // the compiler puts s_waitcnt vmcnt(0) in front of the copy, in the
-    // middle of the burst
-    const float4 gbv = *reinterpret_cast<const float4*>((tid < CS_D / 4 ? a.g0 : a.b0) + 4 * (tid % (CS_D / 4)));
+    // unconditional, as bo below (threads CS_D / 2.. read b0 again and drop it)
+    f32x4 gbv = gld4((tid < CS_D / 4 ? a.g0 : a.b0) + 4 * (tid % (CS_D / 4)));
     // wave w: units (w*2 + j)*16 .. +15 of all CS_MT1 frame tiles; D[unit 4g + e][frame mt*16 + fr]
-    float4 xv[2][CS_MT1], bo4[2];
-    bf16x8 fwo[2][CS_D / 32];
+    f32x4 xv[2][CS_MT1], bo4[2];
     const float* bop = a.bo ? a.bo : a.g0;  // a null bo reads g0 instead and is zeroed at the residual add
 #pragma unroll
-    for (int j = 0; j < 2; ++j) bo4[j] = *reinterpret_cast<const float4*>(bop + (w * 2 + j) * 16 + 4 * g);
-    // The first data barrier needs o and the parameter rows only, and a wave
-    // reaches it only after it has issued every load in front of it: the
-    // CU's one vector-memory queue returns in order and issue stalls while
-    // it is full.  So: a bare s_barrier (it waits for no data) puts every
-    // wave's o requests ahead of any wave's wo request; only the wo
-    // fragments of the first CS_WO_AHEAD K-steps are issued before o is
-    // staged; the rest of wo and all of x (needed only at the residual add)
-    // are issued K-step by K-step behind the MFMAs.  All plain loads, their
-    // order in the instruction stream held by sched_barrier, so the
-    // compiler's own counted vmcnt waits start K-step kk when its two
-    // fragments are in.
-    constexpr int KS = CS_D / 32;
-    auto ld_wo = [&](int kk) __attribute__((always_inline)) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) fwo[j][kk] = ld8(a.wo + (long long)((w * 2 + j) * 16 + fr) * CS_D + fk + kk * 32);
-    };
-    auto ld_x = [&](int i) __attribute__((always_inline)) {
-      const int j = i / CS_MT1, mt = i - j * CS_MT1;
-      const int f = min(max(f0 + mt * 16 + fr, 0), a.T - 1);
-      xv[j][mt] = *reinterpret_cast<const float4*>(a.x + (ubase + f) * CS_D + (w * 2 + j) * 16 + 4 * g);
-    };
+    for (int j = 0; j < 2; ++j) bo4[j] = gld4(bop + (w * 2 + j) * 16 + 4 * g);
+    constexpr int NA = OC + 1 + 2;  // loads in front of the first data barrier: o, the LN0 affine, bo
+    // The first data barrier needs o and the parameter rows only.  The CU's
+    // one vector-memory queue returns in order and issue stalls while it is
+    // full, so: a bare s_barrier (it waits for no data) puts every wave's o
+    // requests ahead of any wave's wo request; the first two of wo's four
+    // tiles (sbk_wo_image: 256 rows x 64 k, this wave's 32 rows one 4 KB run)
+    // follow by LDS-DMA into the ring -- Us and the front of Cv, free until
+    // LN0 writes U; LN0's scratch sits past the second slot -- and land while o
+    // is staged; tile kt + 2 is issued when tile kt's fragments are in VGPRs;
+    // x (needed only at the residual add) goes behind the last tile, so that
+    // no wo tile waits for x in the in-order queue.
+    constexpr int KT = CS_WOT;  // wo tiles = K-steps of 64
+    bf16_t* wslot[2] = {Us, reinterpret_cast<bf16_t*>(Cv)};
+    static_assert(CS_TILE * 2 <= CS_OFF_G, "a wo slot fits in Us");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    cs_issue(a.wo, 0, wslot[0], w, lane);
+    cs_issue(a.wo, 1, wslot[1], w, lane);
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // the NA loads landed, the two tiles stay in flight
+    static_assert(NA == 8, "the burst's loads in front of the two tiles");
 #pragma unroll
-    for (int kk = 0; kk < CS_WO_AHEAD; ++kk) {
-      ld_wo(kk);
-      __builtin_amdgcn_sched_barrier(0);  // K order, not address order
-    }
-    SBK_PROBE(for (int i = 0; i < OC; ++i) asm volatile("" : "+v"(ov[i].x));)
+    for (int i = 0; i < OC; ++i) asm volatile("" : "+v"(ov[i]));
+    vtie(gbv);
+    vtie(bo4[0]);
+    vtie(bo4[1]);
     CS_TL(9);  // o landed
 #pragma unroll
     for (int i = 0; i < OC; ++i) {
       const int c = tid + i * CS_NT;
       const int r = c / (CS_D / 8), ch = c - r * (CS_D / 8), f = f0 + r;
       const bool live = r < nrows && f >= 0 && f < a.T;
-      *reinterpret_cast<uint4*>(Gs + r * CS_S + ((ch * 8) ^ ffn_sw(r))) = live ? ov[i] : uint4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<cs_u4*>(Gs + r * CS_S + ((ch * 8) ^ ffn_sw(r))) = live ? ov[i] : cs_u4{0u, 0u, 0u, 0u};
     }
-    if (tid < CS_D / 2) *reinterpret_cast<float4*>(gb0s + 4 * tid) = gbv;
+    if (tid < CS_D / 2) *reinterpret_cast<f32x4*>(gb0s + 4 * tid) = gbv;
     stage();
     cs_barrier();
     CS_TL(1);
@@ -207,35 +219,61 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) acc[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    SBK_PROBE(asm volatile("" : "+v"(fwo[0][0]), "+v"(fwo[1][0]));)
-    CS_TL(10);  // the first K-step's wo fragments landed: first MFMA
+    // K order kk = 2 kt + ks = 0 .. 7 and the operand roles are those of the
+    // fragment loads this replaces: every accumulator sees the same MFMAs
 #pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-#pragma unroll
-      for (int mt = 0; mt < CS_MT1; ++mt) {
-        const bf16x8 fo = *reinterpret_cast<const bf16x8*>(Gs + (mt * 16 + fr) * CS_S + kk * 32 + fks);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[j][mt] = FFN_MFMA(fwo[j][kk], fo, acc[j][mt]);
+    for (int kt = 0; kt < KT; ++kt) {
+      // tile kt landed; behind it in the queue: the next tile, and x once issued
+      if (kt == 0 || kt == 1)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else if (kt == 2)
+        asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+      static_assert(KT == 4 && 2 * CS_MT1 == 10, "the counted waits above");
+      if (kt == 0) {
+        CS_TL(10);  // the first wo tile landed: first MFMA
       }
-      // K-step kk + 1 stays behind K-step kk, and behind the loads issued in between
-      __builtin_amdgcn_sched_barrier(0);
-      if (kk + CS_WO_AHEAD < KS) ld_wo(kk + CS_WO_AHEAD);
+      bf16x8 fw[2][2];
 #pragma unroll
-      for (int i = kk * (2 * CS_MT1) / KS; i < (kk + 1) * (2 * CS_MT1) / KS; ++i) ld_x(i);
-      __builtin_amdgcn_sched_barrier(0);
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) fw[ks][j] = cs_frag(wslot[kt & 1], w * 32 + j * 16 + fr, ks * 4 + g);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (kt + 2 < KT) cs_issue(a.wo, kt + 2, wslot[kt & 1], w, lane);  // the slot's fragments are in VGPRs
+      if (kt + 2 == KT - 1) {
+#pragma unroll
+        for (int i = 0; i < 2 * CS_MT1; ++i) {
+          const int j = i / CS_MT1, mt = i - j * CS_MT1;
+          const int f = min(max(f0 + mt * 16 + fr, 0), a.T - 1);
+          xv[j][mt] = gld4(a.x + (ubase + f) * CS_D + (w * 2 + j) * 16 + 4 * g);
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int mt = 0; mt < CS_MT1; ++mt) {
+          const bf16x8 fo = *reinterpret_cast<const bf16x8*>(Gs + (mt * 16 + fr) * CS_S + (kt * 2 + ks) * 32 + fks);
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[j][mt] = FFN_MFMA(fw[ks][j], fo, acc[j][mt]);
+        }
     }
     SBK_PROBE(asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__float_as_int(acc[1][CS_MT1 - 1][0]))));)
     CS_TL(11);  // last MFMA retired
-    SBK_PROBE(for (int j = 0; j < 2; ++j) for (int mt = 0; mt < CS_MT1; ++mt) asm volatile("" : "+v"(xv[j][mt].x));)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int mt = 0; mt < CS_MT1; ++mt) vtie(xv[j][mt]);
     CS_TL(12);  // x landed
-    if (!a.bo) bo4[0] = bo4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!a.bo) bo4[0] = bo4[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     float xa[2][CS_MT1][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) {
-        const v2f lo = v2f{xv[j][mt].x, xv[j][mt].y} + (v2f{acc[j][mt][0], acc[j][mt][1]} + v2f{bo4[j].x, bo4[j].y});
-        const v2f hi = v2f{xv[j][mt].z, xv[j][mt].w} + (v2f{acc[j][mt][2], acc[j][mt][3]} + v2f{bo4[j].z, bo4[j].w});
+        const v2f lo = v2f{xv[j][mt][0], xv[j][mt][1]} + (v2f{acc[j][mt][0], acc[j][mt][1]} + v2f{bo4[j][0], bo4[j][1]});
+        const v2f hi = v2f{xv[j][mt][2], xv[j][mt][3]} + (v2f{acc[j][mt][2], acc[j][mt][3]} + v2f{bo4[j][2], bo4[j][3]});
         xa[j][mt][0] = lo[0];
         xa[j][mt][1] = lo[1];
         xa[j][mt][2] = hi[0];

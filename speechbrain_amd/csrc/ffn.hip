@@ -110,6 +110,20 @@
 // the MFMAs under the compiler's counted waits.  The stretch ends at 18.1k
 // cycles instead of 25.0k in the probe build, the same bits;
 // conv_chain_kernel<1> and the step: DESIGN section 3, round 11.
+// Round 12: the bytes of that burst.  (1) The conv-stage launches take their
+// tile from sbk::xcd_tile(gridDim.x, blockIdx.x) instead of blockIdx.x.  At
+// T = 376 an utterance has 8 tiles and workgroups are dealt round-robin to
+// the 8 XCDs, so two neighbouring tiles never shared an L2 and each fetched
+// the 30 halo rows of x and o between them from beyond it; now the blocks of
+// one blockIdx.x % 8 own whole utterances.  FETCH_SIZE x 2 per chain launch
+// 54.8 -> 43.8 MB (the halo), conv_tail_kernel 43.1 -> 32.0 MB.  (2) wo goes
+// through a 2-slot ring from an image of its own (sbk_wo_image, cached per
+// weight like the other images; the `wo` argument of sbk_conv_ffn_chain /
+// sbk_conv_ffn_tail is that image) by LDS-DMA, as phases 1 and 3, instead
+// of as fragments into 64 staging VGPRs; every load of phase -1 is asm with
+// a counted wait (convstage.h).  Same MFMA sequence per accumulator, the same
+// bits.  Step, alternating same-box A/B (ms): parent 1.0814, (1) alone
+// 1.0728, (2) alone 1.0710, both 1.0614.
 #include "mfma.h"
 
 using namespace sbk;
@@ -173,6 +187,10 @@ struct IntC {
 };
 
 constexpr int FFN_BM = 48;
+// the conv-stage launches take their tiles in the XCD-contiguous order (a probe build may switch it off)
+#ifndef FFN_XCD_ORDER
+#define FFN_XCD_ORDER 1
+#endif
 constexpr int FFN_PAD = 16;  // LDS row pad (elements): conflict-free b128 reads (8 measured slower)
 constexpr int FFN_NW = 8, FFN_NT = FFN_NW * 64;  // 8 waves: LN'd rows fit in VGPRs (2 waves/SIMD)
 // Xn / Hs rows: element (row, col) at row * stride + (col ^ ffn_sw(row)), the
@@ -423,10 +441,14 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fr = lane & 15, g = lane >> 4, fk = (8 * g) ^ ffn_sw(fr);  // chunk g of the swizzled rows mt*16 + fr
   // rows m0 .. m0 + BM - 1, live below mlim (CONV: the utterance's end, not the flat M)
-  int m0 = blockIdx.x * BM, mlim = a.M;
+  // CONV: the tile comes from the XCD-contiguous order, so that the tiles of
+  // one utterance, which share their halo rows of x and o, share an L2; the
+  // flat-row kernels have no halo and keep the launch order
+  const int tile = CONV && FFN_XCD_ORDER ? xcd_tile(gridDim.x, blockIdx.x) : (int)blockIdx.x;
+  int m0 = tile * BM, mlim = a.M;
   if constexpr (CONV) {
-    const int nblk = (cs->T + BM - 1) / BM, b = blockIdx.x / nblk;
-    m0 = b * cs->T + (blockIdx.x - b * nblk) * BM;
+    const int nblk = (cs->T + BM - 1) / BM, b = tile / nblk;
+    m0 = b * cs->T + (tile - b * nblk) * BM;
     mlim = (b + 1) * cs->T;
   }
   const int NCH = a.H / HC;
@@ -497,8 +519,8 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, const ConvStageArgs* 
       if (tid < D / 2) *reinterpret_cast<float4*>(ga0 + 4 * tid) = gav;
     };
     if constexpr (CONV) {
-      const int nblk = (cs->T + BM - 1) / BM, ub = blockIdx.x / nblk;
-      conv_stage(*cs, a.inv_n, a.npad, smem, ub, (blockIdx.x - ub * nblk) * BM, xres, stage_params);
+      const int nblk = (cs->T + BM - 1) / BM, ub = tile / nblk;
+      conv_stage(*cs, a.inv_n, a.npad, smem, ub, (tile - ub * nblk) * BM, xres, stage_params);
     } else {
       // ---- the source Linear: xres = A Ws^T + bs for the workgroup's 48 rows.
       // The A rows (bf16, Kin <= 768) wait in LDS, row stride Kin + FFN_PAD (as
@@ -1166,6 +1188,18 @@ __global__ void __launch_bounds__(256) conv_image_kernel(const bf16_t* __restric
   }
 }
 
+// the out_proj image of the conv stage's phase -1: tile kt = wo's 256 rows, k
+// kt*64 .., as the phase-3 tiles above
+__global__ void __launch_bounds__(256) wo_image_kernel(const bf16_t* __restrict__ wo, bf16_t* __restrict__ img) {
+  const int n = CS_WOT * 256 * 8;  // 16-B chunks
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int s = i >> 11, rem = i & 2047, r = rem >> 3, jp = rem & 7;
+    const int j = jp ^ ((r >> 1) & 7);
+    *reinterpret_cast<uint4*>(img + (long long)i * 8) =
+        *reinterpret_cast<const uint4*>(wo + (long long)r * CS_D + s * 64 + 8 * j);
+  }
+}
+
 // ---- the weight-stream image.  Tile s (256 rows x 64 k, 32 KB) in the order
 // ffn_kernel streams them: per FFN block (A, then B for a chain) and hidden
 // chunk c of 256 units: K1 = D / 64 tiles of W1 rows c*256.. (k over D), then
@@ -1401,6 +1435,11 @@ SBK_API int sbk_src_ffn_proj(const void* a_, int Kin, const void* simg, long lon
   return 0;
 }
 
+// the tile that launch index `orig` of `nwg` workgroups owns in the XCD-contiguous
+// order of the conv-stage launches, the GEMMs and the attention kernels
+// (sbk::xcd_tile on the host; -1: no such workgroup)
+SBK_API int sbk_xcd_tile(int nwg, int orig) { return nwg > 0 && orig >= 0 && orig < nwg ? xcd_tile(nwg, orig) : -1; }
+
 SBK_API long long sbk_conv_image_elems(int D) { return D == CS_D ? (long long)(CS_P1T + CS_P3T) * CS_TILE : -1; }
 
 SBK_API int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, void* stream) {
@@ -1410,6 +1449,20 @@ SBK_API int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, vo
   hipLaunchKernelGGL(conv_image_kernel, dim3((CS_P1T + CS_P3T) * 8), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const bf16_t*>(w1p), reinterpret_cast<const bf16_t*>(w2),
                      reinterpret_cast<bf16_t*>(img));
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
+// The out_proj weight wo (D, D) bf16 as the conv stage streams it: CS_WOT
+// tiles of 256 rows x 64 k in the ring's format (as many elements as wo).
+// sbk_conv_ffn_chain / sbk_conv_ffn_tail take this image as their `wo`.
+SBK_API long long sbk_wo_image_elems(int D) { return D == CS_D ? (long long)CS_WOT * CS_TILE : -1; }
+
+SBK_API int sbk_wo_image(const void* wo, int D, void* img, void* stream) {
+  if (D != CS_D || !wo || !img || wo == img) return SBK_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(wo) | reinterpret_cast<uintptr_t>(img)) & 15) return SBK_ERR_ARG;
+  hipLaunchKernelGGL(wo_image_kernel, dim3(CS_WOT * 8), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const bf16_t*>(wo), reinterpret_cast<bf16_t*>(img));
   SBK_CHECK_LAUNCH();
   return 0;
 }

@@ -313,9 +313,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(const T* __restrict__ A, int 
   const int ntn = (N + BN - 1) / BN;
   // XCD-aware remap (bijective): workgroups dealt round-robin to the 8 XCDs get
   // consecutive tiles per XCD, so the N-tiles of one A row-panel share an L2.
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
   const int m0 = (tile_id / ntn) * BM;
   const int n0 = (tile_id % ntn) * BN;
   // full-row (BN == 256) tiles are sbk_gemm_ln's: the residual rows of the
@@ -465,9 +463,7 @@ __global__ void __launch_bounds__(256) gemm_ring_kernel(const bf16_t* __restrict
   const int wm = w >> 1, wn = w & 1;
   const int fr = lane & 15, g = lane >> 4;
   const int ntn = (N + BN - 1) / BN;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
   const int m0 = (tile_id / ntn) * BM;
   const int n0 = (tile_id % ntn) * BN;
   const int nk = K / BK;
@@ -592,9 +588,7 @@ __global__ void __launch_bounds__(256) gemm_pf_kernel(const bf16_t* __restrict__
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int ntn = (N + BN - 1) / BN;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
   const int m0 = (tile_id / ntn) * BM;
   const int n0 = (tile_id % ntn) * BN;
   const int nk = (K + BK - 1) / BK;

@@ -139,8 +139,7 @@ struct G256 {
 // remap (workgroup i runs on XCD i % 8; each XCD walks a contiguous range),
 // then row panels in groups of 8 walked column by column
 __device__ __forceinline__ void tile_of(int orig, int ntn, int ntm, int& tm, int& tn) {
-  const int nwg = ntn * ntm, xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_tile(ntn * ntm, orig);
   constexpr int GM = 8;  // row panels per group; a group is walked column by column
   const int gsz = GM * ntn, grp = wg / gsz, first = grp * GM, gm = min(GM, ntm - first);
   const int in = wg - grp * gsz;

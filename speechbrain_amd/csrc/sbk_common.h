@@ -37,6 +37,16 @@ namespace sbk {
 
 constexpr int kWave = 64;
 
+// XCD-contiguous tile order.  Workgroups are dealt round-robin to the 8 XCDs
+// (blocks with equal blockIdx % 8 share one, and its L2), so launch index
+// `orig` of `nwg` takes the tile at position orig / 8 of residue orig % 8's
+// contiguous run: runs of nwg / 8 tiles, the first nwg % 8 residues one more.
+// A bijection of [0, nwg) for every nwg; placement is a matter of speed only.
+__host__ __device__ __forceinline__ int xcd_tile(int nwg, int orig) {
+  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+}
+
 // Opt a kernel into `bytes` of dynamic LDS (> 64 KB needs it) on the current
 // device.  hipFuncSetAttribute is per device, so the record is per (kernel,
 // device), and it keeps the largest size set so far: a later launch asking
