@@ -974,6 +974,37 @@ int sbk_lstm_bwd(int bf16, int D, const void* w_hhT, const float* cx, const floa
                  const float* dy, const float* dhn, const float* dcn, const int* lens, int B, int T, int H,
                  float* dG, float* dw, float* dhx, float* dcx, void* stream);
 
+/* ---- ligru.hip: LiGRU recurrence (nnet/RNN.py:961-1325), one or two directions ---- */
+
+/* The T forward launches of one LiGRU layer:
+ *   gates = wn[:, t] + h U^T;  a, zpre = the halves of gates;  z = sigmoid(zpre)
+ *   h' = z * h + (1 - z) * act(a) * mask[row]
+ * D = 1 or 2 directions in the same launches, sharing u: launch s works on
+ * frame s in direction 0 and T-1-s in direction 1, and both read the same
+ * raw[b, t].  bf16 != 0: u (2H, H) is bf16 and the h operand is rounded to
+ * bf16; else fp32 and exact-fp32 MFMA.  The state is fp32 in both.  raw
+ * (B, T, 2H) fp32 is the input projection before normalisation; the epilogue
+ * forms wn = (raw - mu[row]) * rs[row] * cscale[col] + cshift[col] with mu, rs
+ * (B*T) both given or both null and cscale, cshift (2H) each or null.  hx
+ * (D, B, H) or null (zeros); mask (D, B, H) or null (ones).  act: 0 ReLU,
+ * 1 LeakyReLU(0.01), 2 tanh, 3 sin.  out (B, T, D*H) = h after every step;
+ * save (B, T, D, 2H) or null = a, z for the backward.  Any B, T, H >= 1.  A
+ * null required pointer, one of mu / rs without the other, a size <= 0, D
+ * outside {1, 2}, act outside 0..3, 2*H*H or 4*B*T*D past int32: 1001. */
+int sbk_ligru_fwd(int bf16, int D, int act, const void* u, const float* hx, const float* raw, const float* mu,
+                  const float* rs, const float* cscale, const float* cshift, const float* mask, int B, int T, int H,
+                  float* out, float* save, void* stream);
+
+/* The T backward launches (order mirrored per direction) and one more for
+ * the carry into dhx.  uT = U^T (H, 2H) in the compute dtype; hx, mask, out,
+ * save as given to / written by sbk_ligru_fwd; dy (B, T, D*H) or null.
+ * Writes dG (B, T, D, 2H) fp32 at true frame positions — the gradient of
+ * the gate pre-activations; the gradient of wn is the sum over D — and dhx
+ * (D, B, H).  dhw (2, D, B, H) fp32 is scratch.  No atomics. */
+int sbk_ligru_bwd(int bf16, int D, int act, const void* uT, const float* hx, const float* out, const float* save,
+                  const float* mask, const float* dy, int B, int T, int H, float* dG, float* dhw, float* dhx,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,19 @@ for the LSTM's reverse direction.
 
 The GRU is unidirectional only (`bidirectional=True` raises
 NotImplementedError); device tensors only (SbkError, no fallback).
+
+LiGRU and LiGRU_Layer (RNN.py:961-1325; csrc/ligru.hip) are drop-ins for the
+reference's own two-gate cell: same constructors, forward(x, hx=None) ->
+(output, h) and state_dict (rnn.{i}.w.weight, rnn.{i}.u.weight, rnn.{i}.norm.*,
+rnn.{i}.h_init, rnn.{i}.drop_masks, rnn.{i}.drop_mask_te), seeded
+construction included.  Per layer one input GEMM serves both directions (the
+reference's cat([x, x.flip(1)]) makes the reverse half's pre-activations the
+flip of the forward half's), the batch / layer normalisation is applied in
+the step kernel's epilogue from per-row and per-column terms, and one launch
+per time step runs both directions on the shared u, forward and backward.  The
+recurrent-dropout pool, its counter and its resampling rules are the
+reference's, in host torch.  The CRDNN lobe that wraps this cell is not
+provided: it needs pooling, BatchNorm and container drop-ins.
 """
 import torch
 
@@ -256,6 +269,243 @@ class _LSTMLayerFn(torch.autograd.Function):
                     grads[4 * d + 3] = db[d * 4 * H:(d + 1) * 4 * H].clone()
         return (dx, None, None, dhx if has_h0 and need[3] else None, dcx if has_c0 and need[4] else None,
                 None, None, None, None, None, *grads)
+
+
+_LIGRU_ACT = {"relu": 0, "leaky_relu": 1, "tanh": 2, "sin": 3}
+
+
+class _LiGRULayerFn(torch.autograd.Function):
+    """One LiGRU layer over a sequence, D = 1 or 2 directions in the same
+    launches and on the same weights.  x (B, T, I); w (2H, I), u (2H, H);
+    gamma, beta (2H); hx, mask (D * B, H) or None (the rows of direction 1
+    after those of direction 0).  kind: "layer" (LayerNorm over the 2H
+    pre-activations of a row), "batch_train" (BatchNorm with the statistics of
+    this call) or "batch_eval" (with rmean, rvar).  Returns the output
+    (B, T, D * H) and the column mean and biased variance of the input
+    projection ("batch_train"; else empty)."""
+
+    @staticmethod
+    def forward(ctx, x, w, u, gamma, beta, hx, mask, rmean, rvar, kind, eps, act, D, dtype, cache, key):
+        H2, I = w.shape
+        H = H2 // 2
+        dev = u.device
+        bf = int(dtype == _bf16)
+        need = any(ctx.needs_input_grad)
+        uk = A.kernel_weight(u, dtype, cache, key + "u")
+        hx0 = None if hx is None else hx.detach().float().contiguous()
+        m0 = None if mask is None else mask.detach().float().contiguous()
+        raw, _, xs, wk, B, T = _input_preact(x, None, [w], None, dtype, cache, key)
+        ga, be = gamma.detach().float(), beta.detach().float()
+        mu = rs = mean = rstd = None
+        if kind == "layer":
+            var, mu = torch.var_mean(raw, dim=1, unbiased=False)
+            rs = torch.rsqrt(var + eps)
+            cscale, cshift = ga.contiguous(), be.contiguous()
+            var, mean = raw.new_empty(0), raw.new_empty(0)
+        else:
+            if kind == "batch_train":
+                var, mean = torch.var_mean(raw, dim=0, unbiased=False)
+            else:
+                var, mean = rvar.detach().float(), rmean.detach().float()
+            rstd = torch.rsqrt(var + eps)
+            cscale = ga * rstd
+            cshift = be - mean * cscale
+        out = torch.empty(B, T, D * H, device=dev, dtype=_f32)
+        save = torch.empty(B, T, D, 2 * H, device=dev, dtype=_f32) if need else None
+        check(lib().sbk_ligru_fwd(bf, D, act, ptr(uk), ptr(hx0), ptr(raw), ptr(mu), ptr(rs), ptr(cscale), ptr(cshift),
+                                  ptr(m0), B, T, H, ptr(out), ptr(save), stream_of(out)), "sbk_ligru_fwd")
+        if need:
+            ctx.save_for_backward(out, save, hx0, m0, raw, mu, rs, mean, rstd, cscale, ga, xs, wk)
+            ctx.cfg = (kind, eps, act, D, dtype, cache, key, B, T, H, I, u, x.dtype)
+        ctx.mark_non_differentiable(mean, var)
+        return out, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, _dmean, _dvar):
+        out, save, hx0, m0, raw, mu, rs, mean, rstd, cscale, ga, xs, wk = ctx.saved_tensors
+        kind, eps, act, D, dtype, cache, key, B, T, H, I, u, xdt = ctx.cfg
+        dev = out.device
+        bf = int(dtype == _bf16)
+        uT = cache.get(key + "uT" + str(bf), [u], lambda: _enc.to_compute(u.detach().t(), dtype))
+        dy = None if dy is None else dy.detach().float().contiguous()
+        dG = torch.empty(B, T, D, 2 * H, device=dev, dtype=_f32)
+        dhw = torch.empty(2, D, B, H, device=dev, dtype=_f32)
+        dhx = torch.empty(D * B, H, device=dev, dtype=_f32)
+        check(lib().sbk_ligru_bwd(bf, D, act, ptr(uT), ptr(hx0), ptr(out), ptr(save), ptr(m0), ptr(dy), B, T, H,
+                                  ptr(dG), ptr(dhw), ptr(dhx), stream_of(out)), "sbk_ligru_bwd")
+        need = ctx.needs_input_grad
+        du = None
+        if need[2]:
+            # the weights are shared: one weight-gradient GEMM over the rows of both directions
+            hp = [_hprev(out[:, :, d * H:(d + 1) * H], None if hx0 is None else hx0[d * B:(d + 1) * B], reverse=d == 1)
+                  for d in range(D)]
+            hp = hp[0] if D == 1 else torch.stack(hp, 1).reshape(B * T * D, H)
+            du = A.wgrad(A._as(dG.view(B * T * D, 2 * H), dtype), A._as(hp, dtype))
+        # gradient of the normalised projection: both directions read the same rows
+        g = dG.view(B * T, 2 * H) if D == 1 else (dG[:, :, 0] + dG[:, :, 1]).view(B * T, 2 * H)
+        M = B * T
+        if kind == "layer":
+            L = lib()
+            nblk = int(L.sbk_layernorm_bwd_blocks(M))
+            part = torch.empty(nblk * 4 * H, device=dev, dtype=_f32)
+            draw = torch.empty(M, 2 * H, device=dev, dtype=_f32)
+            check(L.sbk_layernorm_bwd(ptr(raw), ptr(g), 0, M, 2 * H, ptr(ga), float(eps), None, ptr(draw), ptr(part),
+                                      stream_of(out)), "sbk_layernorm_bwd")
+            gb = A.colsum(part, nblk, 4 * H)
+            dgamma, dbeta = gb[:2 * H], gb[2 * H:]
+        else:
+            xhat = (raw - mean) * rstd
+            dbeta = A.rowsum(g)
+            dgamma = A.rowsum(g * xhat)
+            if kind == "batch_train":
+                # over the reference's doubled batch this is the plain backward with the directions' gradients summed
+                draw = cscale * (g - dbeta / M - xhat * (dgamma / M))
+            else:
+                draw = g * cscale
+        dw, dx = _input_grads(draw, None, 0, I, xs, wk, dtype, xdt, B, T, need[1], need[0])
+        return (dx, dw, du, dgamma if need[3] else None, dbeta if need[4] else None,
+                dhx if hx0 is not None and need[5] else None, None, None, None, None, None, None, None, None, None, None)
+
+
+class LiGRU_Layer(torch.nn.Module):
+    """Drop-in for speechbrain.nnet.RNN.LiGRU_Layer (RNN.py:1125-1325): same
+    constructor, parameters, buffers and forward(x, hx=None) -> h.  The
+    normalisation and the recurrence run in csrc/ligru.hip; the recurrent
+    dropout pool is the reference's, in host torch."""
+
+    def __init__(self, input_size, hidden_size, num_layers, batch_size, dropout=0.0, nonlinearity="relu",
+                 normalization="batchnorm", bidirectional=False):
+        super().__init__()
+        self.hidden_size = int(hidden_size)
+        self.input_size = int(input_size)
+        self.batch_size = batch_size
+        self.bidirectional = bidirectional
+        self.dropout = dropout
+        self.w = torch.nn.Linear(self.input_size, 2 * self.hidden_size, bias=False)
+        self.u = torch.nn.Linear(self.hidden_size, 2 * self.hidden_size, bias=False)
+        if self.bidirectional:
+            self.batch_size = self.batch_size * 2
+        # any other string still normalises with a LayerNorm, as the reference's else branch does
+        if normalization == "batchnorm":
+            self.norm = torch.nn.BatchNorm1d(2 * self.hidden_size, momentum=0.05)
+        else:
+            self.norm = torch.nn.LayerNorm(2 * self.hidden_size)
+        self.normalize = True
+        self.register_buffer("h_init", torch.zeros(1, self.hidden_size))
+        self._init_drop(self.batch_size)
+        # parameter-free: the kernel applies the activation; any other string means ReLU
+        self.act = _LIGRU_ACT.get(nonlinearity, 0)
+        self._wc = _enc.WeightCache()
+
+    def _init_drop(self, batch_size):
+        self.drop = torch.nn.Dropout(p=self.dropout, inplace=False)
+        self.N_drop_masks = 16000
+        self.drop_mask_cnt = 0
+        self.register_buffer("drop_masks", self.drop(torch.ones(self.N_drop_masks, self.hidden_size)).data)
+        self.register_buffer("drop_mask_te", torch.tensor([1.0]).float())
+
+    def _sample_drop_mask(self, device):
+        """The mask rows of this call (RNN.py:1286-1309); None in eval."""
+        if not self.training:
+            return None
+        if self.drop_mask_cnt + self.batch_size > self.N_drop_masks:
+            self.drop_mask_cnt = 0
+            self.drop_masks = self.drop(torch.ones(self.N_drop_masks, self.hidden_size, device=device)).data
+        mask = self.drop_masks[self.drop_mask_cnt:self.drop_mask_cnt + self.batch_size]
+        self.drop_mask_cnt = self.drop_mask_cnt + self.batch_size
+        return mask
+
+    def _change_batch_size(self, rows, device):
+        if self.batch_size != rows:
+            self.batch_size = rows
+            if self.training:
+                self.drop_masks = self.drop(torch.ones(self.N_drop_masks, self.hidden_size, device=device)).data
+
+    def forward(self, x, hx=None):
+        require_device(x, hx, self.w.weight)
+        H, D = self.hidden_size, 2 if self.bidirectional else 1
+        if x.ndim != 3 or x.shape[-1] != self.input_size:
+            raise ValueError(f"LiGRU_Layer expects (batch, time, {self.input_size}) (got {tuple(x.shape)})")
+        B, T, _ = x.shape
+        rows = D * B
+        self._change_batch_size(rows, x.device)
+        mask = self._sample_drop_mask(x.device)
+        if mask is not None and tuple(mask.shape) != (rows, H):
+            raise ValueError(f"the dropout pool yields {tuple(mask.shape)} mask rows for a batch of {rows}")
+        if hx is not None:
+            if hx.shape[-1] != H or hx.numel() not in (H, rows * H):
+                raise ValueError(f"hx must be {(rows, H)} or {(1, H)} (got {tuple(hx.shape)})")
+            hx = hx.reshape(-1, H).expand(rows, H)
+        norm = self.norm
+        batch = isinstance(norm, torch.nn.BatchNorm1d)
+        kind = "layer" if not batch else ("batch_train" if self.training or norm.running_mean is None else "batch_eval")
+        n = rows * T
+        if kind == "batch_train" and n <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[n, 2 * H]}")
+        out, mean, var = _LiGRULayerFn.apply(x, self.w.weight, self.u.weight, norm.weight, norm.bias, hx, mask,
+                                             norm.running_mean if batch else None, norm.running_var if batch else None,
+                                             kind, norm.eps, self.act, D, _enc.compute_dtype(), self._wc, "ligru")
+        if kind == "batch_train" and self.training and norm.running_mean is not None:
+            # torch's update for the reference's row count: both directions' rows, n / (n - 1) unbiased
+            with torch.no_grad():
+                norm.num_batches_tracked += 1
+                mom = norm.momentum if norm.momentum is not None else 1.0 / float(norm.num_batches_tracked)
+                norm.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
+                norm.running_var.mul_(1 - mom).add_(var, alpha=mom * n / (n - 1))
+        return out
+
+
+class LiGRU(torch.nn.Module):
+    """Drop-in for speechbrain.nnet.RNN.LiGRU (RNN.py:961-1122): same
+    constructor, forward(x, hx=None) -> (output, h) and state_dict."""
+
+    def __init__(self, hidden_size, input_shape, nonlinearity="relu", normalization="batchnorm", num_layers=1,
+                 bias=True, dropout=0.0, re_init=True, bidirectional=False):
+        super().__init__()
+        self.hidden_size = hidden_size
+        self.nonlinearity = nonlinearity
+        self.num_layers = num_layers
+        self.normalization = normalization
+        self.bias = bias
+        self.dropout = dropout
+        self.re_init = re_init
+        self.bidirectional = bidirectional
+        self.reshape = False
+        if len(input_shape) > 3:
+            self.reshape = True
+        self.fea_dim = float(torch.prod(torch.tensor(input_shape[2:])))
+        self.batch_size = input_shape[0]
+        self.rnn = self._init_layers()
+        if self.re_init:
+            rnn_init(self.rnn)
+
+    def _init_layers(self):
+        rnn = torch.nn.ModuleList([])
+        current_dim = self.fea_dim
+        for _ in range(self.num_layers):
+            rnn.append(LiGRU_Layer(current_dim, self.hidden_size, self.num_layers, self.batch_size,
+                                   dropout=self.dropout, nonlinearity=self.nonlinearity,
+                                   normalization=self.normalization, bidirectional=self.bidirectional))
+            current_dim = self.hidden_size * 2 if self.bidirectional else self.hidden_size
+        return rnn
+
+    def forward(self, x, hx=None):
+        require_device(x, hx, self.rnn[0].w.weight)
+        if self.reshape and x.ndim == 4:
+            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
+        h = []
+        if hx is not None and self.bidirectional:
+            hx = hx.reshape(self.num_layers, self.batch_size * 2, self.hidden_size)
+        for i, lay in enumerate(self.rnn):
+            x = lay(x, hx=None if hx is None else hx[i])
+            h.append(x[:, -1, :])
+        # the reference's own ops: the bidirectional form is a raw reshape, not a transpose
+        h = torch.stack(h, dim=1)
+        if self.bidirectional:
+            h = h.reshape(h.shape[1] * 2, h.shape[0], self.hidden_size)
+        else:
+            h = h.transpose(0, 1)
+        return x, h
 
 
 class _Recurrent(torch.nn.Module):
