@@ -341,6 +341,16 @@ int sbk_xcd_tile(int nwg, int orig);
 long long sbk_wo_image_elems(int D);
 int sbk_wo_image(const void* wo, int D, void* img, void* stream);
 
+/* The depthwise taps wc (K, D) fp32, tap-major, and the conv bias bc (D) or
+ * null as the conv stage of sbk_conv_ffn_chain / sbk_conv_ffn_tail reads them:
+ * 16 rows of D words, word c of row j = taps 2j, 2j + 1 of channel c rounded
+ * to bf16 (low, high half; taps >= K are zero), then a row of D fp32 biases
+ * (zero for a null bc): sbk_dw_image_elems(D) 32-bit words.  Those two entry
+ * points take this image as their `dwimg` argument; sbk_conv_module_pre takes
+ * wc and bc themselves.  D = 256, 1 <= K <= 31; img 16-byte aligned. */
+long long sbk_dw_image_elems(int D);
+int sbk_dw_image(const float* wc, const float* bc, int K, int D, void* img, void* stream);
+
 /* Weight-stream image of the convolution-module stage of sbk_conv_ffn_chain:
  * w1p (2D, D) GLU-permuted and w2 (D, D) bf16 as 12 tiles of 256 rows x 64 k
  * in stream order (8 of w1p: per 64 k, the first then the second GLU group of
@@ -352,12 +362,14 @@ int sbk_conv_image(const void* w1p, const void* w2, int D, void* img, void* stre
  * projection tail (np > 0) in one launch, one workgroup per 48-frame tile of
  * one utterance: the convolution module's output rows stay on the CU as the
  * chain's input and residual.  c* arguments: the convolution module's (as
- * sbk_conv_module_pre, except that wo is sbk_wo_image(wo), not wo itself;
+ * sbk_conv_module_pre, except that wo is sbk_wo_image(wo), not wo itself, and
+ * that dwimg = sbk_dw_image(wc, bc) stands for the taps: it carries the conv
+ * bias, so bc is not read here and keeps its place in the list only;
  * cimg = sbk_conv_image(w1p, w2)); H .. yp: the chain's (as sbk_ffn_chain).  out (B*T, D) fp32 receives block B's output and must
  * not alias x; yp (B*T, np) bf16.  D = 256, K <= 31. */
 int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D, int d_eff,
                        const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg, long long cimg_elems,
-                       const float* cb1p, const float* wc, const float* bc, int K, int causal, const float* cln1_w,
+                       const float* cb1p, const void* dwimg, const float* bc, int K, int causal, const float* cln1_w,
                        const float* cln1_b, float ceps1, const float* cb2, const unsigned char* kpm, int H, int act,
                        float slope, const float* g0, const float* b0, float eps0, const float* b1, const float* b2,
                        float alpha, const float* gp, const float* bp, float epsp, const float* g0b, const float* b0b,
@@ -374,7 +386,7 @@ int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const floa
  * module's output and the pre-LN rows stay on the CU); u must not alias x. */
 int sbk_conv_ffn_tail(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D, int d_eff,
                       const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg, long long cimg_elems,
-                      const float* cb1p, const float* wc, const float* bc, int K, int causal, const float* cln1_w,
+                      const float* cb1p, const void* dwimg, const float* bc, int K, int causal, const float* cln1_w,
                       const float* cln1_b, float ceps1, const float* cb2, const unsigned char* kpm, int H, int act,
                       float slope, const float* g0, const float* b0, float eps0, const float* b1, const float* b2,
                       float alpha, const float* gp, const float* bp, float epsp, const float* gn, const float* bn,

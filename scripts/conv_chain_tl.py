@@ -42,10 +42,11 @@ buf = (ctypes.c_ulonglong * (16 * 256))()
 lib = ctypes.CDLL(_L.LIB_PATH)
 assert lib.sbk_probe_ffn_tl(buf) == 0
 tl = np.array(buf, dtype=np.int64).reshape(16, 256)
-# marks in program order: conv stage 210 .. 218 (its start split by 219 .. 222), chain 1, A steps, 197 .. 198, B steps, 194 .. 196
+# marks in program order: conv stage 210 .. 218 (its start split by 219 .. 222, its middle phases by 223 .. 229), chain 1, A steps, 197 .. 198, B steps, 194 .. 196
 names = [("start", 0), ("cs in", 210), ("o landed", 219), ("staged", 211), ("wo k0 landed", 220), ("last mfma", 221),
-         ("x landed", 222), ("out_proj+sums", 212), ("LN0", 213), ("ph1 gemm", 214),
-         ("GLU", 215), ("ph2a", 216), ("ph2b", 217), ("ph3", 218), ("A LN0 (loop)", 1), ("A steps", 3 + 2 * 31),
+         ("x landed", 222), ("xres reloc", 227), ("out_proj+sums", 212), ("xchg bar 1", 228), ("xchg bar 2", 229),
+         ("LN0", 213), ("ph1 gemm", 214), ("b1 landed", 223), ("GLU", 215), ("taps landed", 224), ("window", 225),
+         ("ph2a", 216), ("2b params", 226), ("ph2b", 217), ("ph3", 218), ("A LN0 (loop)", 1), ("A steps", 3 + 2 * 31),
          ("seam in", 197), ("seam z", 200), ("postLN", 201), ("LN0b", 202), ("Xn bar", 203), ("frags", 198),
          ("B steps", 3 + 2 * 63), ("epi in", 194), ("epi z", 195), ("nextLN", 204), ("Zo/Xn bar", 205),
          ("proj", 206), ("end", 196)]

@@ -394,6 +394,32 @@ def wo_image(wo):
     return _WO_IMAGES.get((wo,), 0, torch.cuda.current_stream(wo.device), build=_build_wo_image)
 
 
+_DW_IMAGES = _ImageCache()
+
+
+def _build_dw_image(ws, np_, stream):
+    wc, bc = ws
+    K, D = wc.shape
+    n = int(lib().sbk_dw_image_elems(D))
+    if n <= 0 or (bc is not None and tuple(bc.shape) != (D,)):
+        raise SbkError(f"sbk_dw_image: unsupported shapes {tuple(wc.shape)}, {None if bc is None else tuple(bc.shape)}")
+    img = torch.empty(n, device=wc.device, dtype=torch.int32)
+    check(lib().sbk_dw_image(ptr(wc), ptr(bc), K, D, ptr(img), ctypes.c_void_p(stream.cuda_stream)), "sbk_dw_image")
+    return img
+
+
+def dw_image(wc, bc=None):
+    """The depthwise taps wc (K, D) fp32, tap-major, and the conv bias bc (D)
+    fp32 or None as the conv stage of conv_ffn_chain / conv_ffn_tail reads them
+    (packed bf16 tap pairs, pair-major, then the bias row; int32 words); cached
+    per tensors (and versions) as the other images.  The entry lives as long as
+    both tensors do: a caller that wants the hit keeps them (fused_params does)."""
+    for t in (wc, bc):
+        if t is not None and (t.dtype != _f32 or not t.is_contiguous()):
+            raise TypeError("dw_image: contiguous fp32 taps and bias")
+    return _DW_IMAGES.get((wc, bc), 0, torch.cuda.current_stream(wc.device), build=_build_dw_image)
+
+
 @custom_op("sbk::ffn", mutates_args=())
 def _ffn_op(x: torch.Tensor, g0: torch.Tensor, b0: torch.Tensor, e0: float, w1: torch.Tensor, b1: torch.Tensor,
             act: int, slope: float, w2: torch.Tensor, b2: torch.Tensor, alpha: float, gp: Optional[torch.Tensor],
@@ -615,9 +641,10 @@ def _conv_ffn_chain_into(out, y, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc
     H, NP = w1.shape[0], wp.shape[0]
     cimg = conv_image(w1p, cw2)
     woimg = wo_image(wo)
+    dwimg = dw_image(wc, bc)
     img = ffn_image(w1, w2, w1b, w2b, wp)
     rc = lib().sbk_conv_ffn_chain(ptr(x), ptr(o), ptr(woimg), ptr(bo), B, T, D, deff, ptr(cg0), ptr(cb0), float(ce0),
-                                  ptr(cimg), cimg.numel(), ptr(b1p), ptr(wc), ptr(bc), wc.shape[0], int(causal),
+                                  ptr(cimg), cimg.numel(), ptr(b1p), ptr(dwimg), None, wc.shape[0], int(causal),
                                   ptr(cg1), ptr(cb1), float(ce1), ptr(cb2), ptr(kpm), H, act, float(slope), ptr(g0),
                                   ptr(b0), float(e0), ptr(b1), ptr(b2), float(alpha), ptr(gp), ptr(bp), float(ep),
                                   ptr(g0b), ptr(b0b), float(e0b), ptr(b1b), ptr(b2b), float(alphab), ptr(out), ptr(gn),
@@ -679,9 +706,10 @@ def _conv_ffn_tail_into(u, x, B, T, o, wo, bo, cg0, cb0, ce0, w1p, b1p, wc, bc, 
     """The launch of sbk::conv_ffn_tail into caller-owned u (>= B*T rows of D fp32)."""
     cimg = conv_image(w1p, cw2)
     woimg = wo_image(wo)
+    dwimg = dw_image(wc, bc)
     img = ffn_image(w1, w2)
     rc = lib().sbk_conv_ffn_tail(ptr(x), ptr(o), ptr(woimg), ptr(bo), B, T, x.shape[1], deff, ptr(cg0), ptr(cb0),
-                                 float(ce0), ptr(cimg), cimg.numel(), ptr(b1p), ptr(wc), ptr(bc), wc.shape[0],
+                                 float(ce0), ptr(cimg), cimg.numel(), ptr(b1p), ptr(dwimg), None, wc.shape[0],
                                  int(causal), ptr(cg1), ptr(cb1), float(ce1), ptr(cb2), ptr(kpm), w1.shape[0], act,
                                  float(slope), ptr(g0), ptr(b0), float(e0), ptr(b1), ptr(b2), float(alpha), ptr(gp),
                                  ptr(bp), float(ep), ptr(gn), ptr(bn), float(en), ptr(u), ptr(img), img.numel(),

@@ -76,6 +76,8 @@ SIGNATURES = {
     "sbk_xcd_tile": [_i, _i],
     "sbk_wo_image_elems": [_i],
     "sbk_wo_image": [_vp, _i, _vp, _vp],
+    "sbk_dw_image_elems": [_i],
+    "sbk_dw_image": [_vp, _vp, _i, _i, _vp, _vp],
     "sbk_conv_image_elems": [_i],
     "sbk_conv_image": [_vp, _vp, _i, _vp, _vp],
     "sbk_conv_ffn_chain": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _ll, _vp, _vp, _vp, _i, _i, _vp, _vp,
@@ -203,7 +205,7 @@ SIGNATURES = {
     "sbk_joint_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "sbk_joint_bwd_workspace_floats": [_i, _i, _i, _i],
 }
-RESTYPES = {"sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_conv_image_elems": ctypes.c_longlong, "sbk_wo_image_elems": ctypes.c_longlong, "sbk_src_image_elems": ctypes.c_longlong,"sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong, "sbk_ctc_workspace_floats": ctypes.c_longlong}
+RESTYPES = {"sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_conv_image_elems": ctypes.c_longlong, "sbk_wo_image_elems": ctypes.c_longlong, "sbk_dw_image_elems": ctypes.c_longlong, "sbk_src_image_elems": ctypes.c_longlong,"sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong, "sbk_ctc_workspace_floats": ctypes.c_longlong}
 
 _lib = None
 _load_error = None

@@ -38,6 +38,21 @@
 // 15.2k with the XCD-contiguous tile order of ffn.hip round 12.  The K loop
 // is still 5.6k cycles for 80 MFMAs per wave: ~1.4k per tile, one tile's
 // fetch latency, since a 2-slot ring has one tile in flight.
+// Round 13: the small launch-constant parameter vectors of the middle phases
+// were each fetched behind their phase's barrier and waited for at once, by
+// all eight waves, with nothing else in flight.  Now each is on its way one
+// phase early, by loads the compiler cannot see and a counted wait at first
+// use: phase 1's bias b1 rides in the launch-start burst (threads that re-read
+// b0 and dropped it) into LDS beside the LN0 affine; phase 2a's taps and bias
+// come as 17 words per thread from an image (sbk_dw_image: the bf16 rounding
+// and pairing that every workgroup of every launch did on 32 fp32 loads),
+// issued behind phase 1's K loop; phase 2b's LN1 affine, b2 and the mask
+// bytes go out at the head of phase 2a.  Middle phases of workgroup 128
+// (probe builds, same box, cycles): GLU epilogue 3.5k -> 3.2k, phase 2a 7.4k
+// -> 6.1k, phase 2b 5.1k -> 4.4k; the launch ends 2.4-2.7k earlier.  Measured
+// equal and not kept: the residual's 24 ds_bpermute behind LN0's partial-sum
+// stores, the statistics waves reducing before they issue phase 1's tiles, and
+// sched_group_barriers for a deeper pipeline of phase 2a's window reads.
 #pragma once
 
 struct ConvStageArgs {
@@ -47,8 +62,7 @@ struct ConvStageArgs {
   float eps0;
   const bf16_t* img;  // sbk_conv_image(w1p, w2)
   const float* b1;    // (2D) permuted like w1p
-  const float* wc;    // (K, D) depthwise taps, tap-major
-  const float* bc;    // (D) or null
+  const uint32_t* dw; // sbk_dw_image of the depthwise taps and the conv bias
   const float *g1, *b1n;  // LN1
   float eps1;
   const float* b2;      // (D) or null
@@ -66,10 +80,17 @@ constexpr int CS_S = CS_D + FFN_PAD;  // U / G row stride: rows swizzled by ffn_
 constexpr int CS_TILE = 256 * 64;     // elements of an image tile
 constexpr int CS_P1T = 8, CS_P3T = 4; // image tiles of phase 1 (4 K-steps x 2 group halves) and phase 3
 constexpr int CS_WOT = CS_D / 64;     // image tiles of the out_proj weight (sbk_wo_image)
+constexpr int CS_NP = (CS_KMAX + 1) / 2;  // depthwise tap pairs (tap 31 is zero)
+// sbk_dw_image: CS_NP rows of CS_D packed bf16 tap pairs (pair-major: a wave's
+// load of one pair is one 256-B run), then a row of fp32 conv biases (0 for none)
+constexpr int CS_DW_WORDS = (CS_NP + 1) * CS_D;
 // LDS (bytes): U/V, G, the fp32 conv tile; ring slot 0 over G, slot 1 over the conv tile's front
 constexpr int CS_OFF_G = CS_ROWS * CS_S * 2, CS_OFF_CV = 2 * CS_OFF_G;
 constexpr int CS_LDS = CS_OFF_CV + CS_BM * CS_D * 4;
 static_assert(CS_TILE * 2 <= CS_OFF_G && CS_TILE * 2 <= CS_BM * CS_D * 4, "ring slots fit");
+// LN0's affine and phase 1's bias, staged by the prologue (floats into the conv
+// tile: past ring slot 1, the LN0 partials and statistics)
+constexpr int CS_GB0 = CS_TILE / 2 + 2 * CS_ROWS * (CS_NW + 4) + 2 * CS_ROWS;
 
 // wave w's 4 KB of an image tile -> its 4 KB of a ring slot, four 1-KB LDS-DMA
 // pieces from one base (the instruction offset applies to both addresses).
@@ -101,6 +122,13 @@ typedef unsigned int cs_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ cs_u4 cs_gld16(const bf16_t* p) {
   cs_u4 v;
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+// one dword at p + OFF bytes, likewise
+template <int OFF>
+__device__ __forceinline__ uint32_t cs_gldw(const uint32_t* p) {
+  uint32_t v;
+  asm volatile("global_load_dword %0, %1, off offset:%2" : "=v"(v) : "v"(p), "n"(OFF) : "memory");
   return v;
 }
 __device__ __forceinline__ int cs_gldu8(const uint8_t* p) {
@@ -167,10 +195,18 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     // LN0's scratch (partials, statistics, affine) sits past ring slot 1
     float* lnscr = Cv + CS_TILE / 2;
     constexpr int RS = CS_NW + 4;  // partial-row stride (floats), 16-B aligned
-    static_assert(CS_TILE / 2 + 2 * CS_ROWS * RS + 2 * CS_ROWS + 2 * CS_D <= CS_BM * CS_D, "LN0 scratch fits");
-    float* gb0s = lnscr + 2 * CS_ROWS * RS + 2 * CS_ROWS;  // [g0 | b0]
-    // unconditional, as bo below (threads CS_D / 2.. read b0 again and drop it)
-    f32x4 gbv = gld4((tid < CS_D / 4 ? a.g0 : a.b0) + 4 * (tid % (CS_D / 4)));
+    static_assert(CS_TILE / 2 + 2 * CS_ROWS * RS + 2 * CS_ROWS + 4 * CS_D <= CS_BM * CS_D, "LN0 scratch fits");
+    float* gb0s = Cv + CS_GB0;  // [g0 | b0 | b1 (2 CS_D, for the GLU epilogue)]
+    static_assert(CS_GB0 == CS_TILE / 2 + 2 * CS_ROWS * RS + 2 * CS_ROWS, "behind the partials and the statistics");
+    // unconditional, as bo below (threads CS_D.. read b0 again and drop it).
+    // Threads CS_D / 2 .. CS_D - 1 used to do the same: they fetch phase 1's
+    // bias b1 instead, at no further load in the burst, and the GLU epilogue
+    // reads it from LDS instead of from L2 behind its barrier
+    static_assert(CS_NT >= CS_D, "one float4 of [g0 | b0 | b1] per thread");
+    f32x4 gbv = gld4(tid < CS_D / 4   ? a.g0 + 4 * tid
+                     : tid < CS_D / 2 ? a.b0 + 4 * (tid - CS_D / 4)
+                     : tid < CS_D     ? a.b1 + 4 * (tid - CS_D / 2)
+                                      : a.b0 + 4 * (tid % (CS_D / 4)));
     // wave w: units (w*2 + j)*16 .. +15 of all CS_MT1 frame tiles; D[unit 4g + e][frame mt*16 + fr]
     f32x4 xv[2][CS_MT1], bo4[2];
     const float* bop = a.bo ? a.bo : a.g0;  // a null bo reads g0 instead and is zeroed at the residual add
@@ -210,7 +246,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
       const bool live = r < nrows && f >= 0 && f < a.T;
       *reinterpret_cast<cs_u4*>(Gs + r * CS_S + ((ch * 8) ^ ffn_sw(r))) = live ? ov[i] : cs_u4{0u, 0u, 0u, 0u};
     }
-    if (tid < CS_D / 2) *reinterpret_cast<f32x4*>(gb0s + 4 * tid) = gbv;
+    if (tid < CS_D) *reinterpret_cast<f32x4*>(gb0s + 4 * tid) = gbv;
     stage();
     cs_barrier();
     CS_TL(1);
@@ -302,6 +338,8 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
           xres[j][mt] = make_float4(v[0], v[1], v[2], v[3]);
         }
     }
+    SBK_PROBE(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");)
+    CS_TL(17);  // the residual's relocation returned
     // LN0 over the 256 units of each frame: 8 per lane, 4 lanes per wave
     // (col4), 8 waves through LDS; sum and sum of squares in one exchange
     // (var = E[x^2] - mean^2 in fp32, as conv_module_kernel<true>)
@@ -325,6 +363,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     }
     CS_TL(2);
     cs_barrier();
+    CS_TL(18);  // first exchange barrier
     // every wave is past its reads of Gs: phase 1's first two tiles land
     // under the statistics exchange and the LN0 application
     cs_issue(a.img, 0, slot[0], w, lane);
@@ -345,6 +384,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
       stat[CS_ROWS + row] = __builtin_amdgcn_rsqf(fmaxf(t2 * inv_n - mu * mu, 0.f) + a.eps0);  // v_rsq_f32, 1 ulp
     }
     cs_barrier();
+    CS_TL(19);  // second exchange barrier
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int u0 = (w * 2 + j) * 16 + 4 * g;
@@ -373,6 +413,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
   // ---- phase 1: G = GLU(U W1p^T + b1p) over CS_ROWS frames.  Tile q = K-step
   // q / 2, half q % 2: wave w's rows of it are GLU group 2w + q % 2 (16 value
   // rows, 16 gate rows)
+  uint32_t tw[CS_NP + 1];  // phase 2a's tap pairs and bias, loaded behind the K loop
   {
     f32x4 acc[2][2][CS_MT1];
 #pragma unroll
@@ -411,6 +452,31 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
 #pragma unroll
           for (int mt = 0; mt < CS_MT1; ++mt) acc[h][t][mt] = FFN_MFMA(fw[ks][t], fa[ks][mt], acc[h][t][mt]);
     }
+    // Phase 2a's taps and bias (sbk_dw_image: packed pairs, pair-major, then
+    // the bias row) go out here, one phase early: the queue is empty, and the
+    // barrier and the GLU epilogue cover their latency.  b1 comes from LDS,
+    // where the prologue put it, read before the barrier for the same reason
+    {
+      const uint32_t* dwp = a.dw + (tid & (CS_D - 1));
+#pragma unroll
+      for (int j4 = 0; j4 < CS_NP; j4 += 4) {
+        tw[j4] = cs_gldw<0>(dwp + j4 * CS_D);
+        tw[j4 + 1] = cs_gldw<CS_D * 4>(dwp + j4 * CS_D);
+        tw[j4 + 2] = cs_gldw<2 * CS_D * 4>(dwp + j4 * CS_D);
+        tw[j4 + 3] = cs_gldw<3 * CS_D * 4>(dwp + j4 * CS_D);
+      }
+      tw[CS_NP] = cs_gldw<0>(dwp + CS_NP * CS_D);
+      static_assert(CS_NP % 4 == 0 && 3 * CS_D * 4 < 4096, "four loads per base, 12-bit offsets");
+    }
+    float4 b1a[2], b1g[2];  // b1 of the value / gate rows of channel group 2w + h
+    {
+      const float* b1s = Cv + CS_GB0 + 2 * CS_D;  // behind [g0 | b0]
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        b1a[h] = *reinterpret_cast<const float4*>(b1s + (w * 2 + h) * 32 + 4 * g);
+        b1g[h] = *reinterpret_cast<const float4*>(b1s + (w * 2 + h) * 32 + 4 * g + 16);
+      }
+    }
     cs_barrier();  // every wave's ring reads are done before G overwrites Gs
     CS_TL(4);
     // GLU epilogue: lane holds frames mt*16 + fr, units 4g..4g+3 of each
@@ -418,10 +484,12 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int ch = (w * 2 + h) * 16 + 4 * g;            // output channels ch .. ch + 3
-      const int pa = (w * 2 + h) * 32 + 4 * g, pg = pa + 16;  // permuted rows of value / gate
-      const float4 ba = *reinterpret_cast<const float4*>(a.b1 + pa);
-      const float4 bg = *reinterpret_cast<const float4*>(a.b1 + pg);
+      const float4 ba = b1a[h], bg = b1g[h];  // permuted rows (w*2 + h)*32 + 4g of value, + 16 of gate
       const v2f bav[2] = {v2f{ba.x, ba.y}, v2f{ba.z, ba.w}}, bgv[2] = {v2f{bg.x, bg.y}, v2f{bg.z, bg.w}};
+      SBK_PROBE(if (h == 0) { asm volatile("" ::"v"(ba.x), "v"(bg.x) : "memory"); })
+      if (h == 0) {
+        CS_TL(13);  // the b1 vectors landed
+      }
 #pragma unroll
       for (int mt = 0; mt < CS_MT1; ++mt) {
         const int r = mt * 16 + fr, f = f0 + r;
@@ -445,26 +513,39 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
 
   // ---- phase 2a: depthwise conv, thread (channel c, half h) over 24 frames,
   // two taps per v_dot2 (bf16 operands, fp32 accumulation) -> fp32 tile
+  // The taps come packed from the image (before: 32 fp32 loads, 32 selects and
+  // 16 packs per thread and launch, issued and waited for here).  Phase 2b's
+  // LN1 affine, phase 3's bias and the key-padding bytes go out in their turn,
+  // one phase early, under the window assembly and the dot loop
+  f32x4 bb2[2], g14, b14;
+  int km[CS_MT3];
   {
     const int c = tid & (CS_D - 1), h = tid >> 8;
     constexpr int NF = CS_BM / (CS_NT / CS_D);
-    constexpr int NP = (CS_KMAX + 1) / 2;  // tap pairs (tap 31 is zero)
-    float wk[2 * NP];
-#pragma unroll
-    for (int k = 0; k < 2 * NP; ++k) {  // (K, D): coalesced; clamped address + select
-      const float v = a.wc[min(k, a.K - 1) * CS_D + c];
-      wk[k] = k < a.K ? v : 0.f;
-    }
-    const float bias = a.bc ? a.bc[c] : 0.f;
+    constexpr int NP = CS_NP;
     static_assert((CS_NT / CS_D - 1) * NF + NF + 2 * NP - 1 <= CS_ROWS, "every window row is staged");
     static_assert(NF % 4 == 0, "h * NF keeps bits 0-1 of the row; frame pairs");
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
     bf2 tp[NP], ev[NF / 2 + NP - 1], od[NF / 2 + NP - 1];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the taps and the bias (nothing else is in flight)
 #pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      tp[j] = __builtin_bit_cast(bf2, pack_bf16x2(wk[2 * j], wk[2 * j + 1]));
-      asm volatile("" : "+v"(tp[j]));
-    }
+    for (int j = 0; j <= NP; ++j) asm volatile("" : "+v"(tw[j]));
+#pragma unroll
+    for (int j = 0; j < NP; ++j) tp[j] = __builtin_bit_cast(bf2, tw[j]);
+    const float bias = __uint_as_float(tw[NP]);
+    CS_TL(14);  // the taps landed
+    SBK_PROBE(asm volatile("" ::: "memory");)
+    g14 = gld4(a.g1 + lane * 4);
+    b14 = gld4(a.b1n + lane * 4);
+    // unconditional (a null b2 / kpm reads g1 instead and is zeroed after the
+    // wait): a load under a branch would be merged with the zero by a
+    // register copy the compiler places before the data has landed
+    const float* b2p = a.b2 ? a.b2 : a.g1;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bb2[j] = gld4(b2p + (w * 2 + j) * 16 + 4 * g);
+#pragma unroll
+    for (int mt = 0; mt < CS_MT3; ++mt)
+      km[mt] = cs_gldu8(a.kpm ? a.kpm + ubase + min(t0 + mt * 16 + fr, a.T - 1) : reinterpret_cast<const uint8_t*>(a.g1));
     // row h * NF + k: its swizzle is ffn_sw(k) ^ ffn_sw(h * NF)
     const int cx = c ^ ffn_sw(h * NF);
     const unsigned short* Gu0 = reinterpret_cast<const unsigned short*>(Gs) + h * NF * CS_S + cx;
@@ -478,6 +559,9 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
       od[r] = __builtin_bit_cast(bf2, g1 | (g2 << 16));
       g0 = g2;
     }
+    SBK_PROBE(for (int r = 0; r < NF / 2 + NP - 1; ++r) asm volatile("" : "+v"(ev[r]), "+v"(od[r])::"memory");)
+    CS_TL(15);  // the window assembled
+    SBK_PROBE(asm volatile("" ::: "memory");)
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
       float s = bias;
@@ -491,21 +575,9 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
 
   // ---- phase 2b: LN1 -> Swish -> V (over U), one wave per frame, 4 channels
   // per lane.  Gs is free: phase 3's first tile lands under this phase (the
-  // LN1 affine and phase 3's bias / key-padding bytes are loaded first and
-  // waited for by count, ahead of it)
-  f32x4 bb2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  int km[CS_MT3] = {};
+  // LN1 affine and phase 3's bias / key-padding bytes are in flight since
+  // phase 2a and are waited for by count, ahead of it)
   {
-    f32x4 g14 = gld4(a.g1 + lane * 4), b14 = gld4(a.b1n + lane * 4);
-    // unconditional (a null b2 / kpm reads g1 instead and is zeroed after the
-    // wait): a load under a branch would be merged with the zero by a
-    // register copy the compiler places before the data has landed
-    const float* b2p = a.b2 ? a.b2 : a.g1;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bb2[j] = gld4(b2p + (w * 2 + j) * 16 + 4 * g);
-#pragma unroll
-    for (int mt = 0; mt < CS_MT3; ++mt)
-      km[mt] = cs_gldu8(a.kpm ? a.kpm + ubase + min(t0 + mt * 16 + fr, a.T - 1) : reinterpret_cast<const uint8_t*>(a.g1));
     cs_issue(a.img, CS_P1T, slot[0], w, lane);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     vtie(g14);
@@ -514,6 +586,7 @@ __device__ __forceinline__ void conv_stage(const ConvStageArgs& a, float inv_n, 
     vtie(bb2[1]);
 #pragma unroll
     for (int mt = 0; mt < CS_MT3; ++mt) asm volatile("" : "+v"(km[mt]));
+    CS_TL(16);  // the LN1 affine, b2 and the mask bytes landed
     if (!a.b2) bb2[0] = bb2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (!a.kpm) km[0] = km[1] = km[2] = 0;
     const v2f gm[2] = {v2f{g14[0], g14[1]}, v2f{g14[2], g14[3]}}, bt[2] = {v2f{b14[0], b14[1]}, v2f{b14[2], b14[3]}};

@@ -1200,6 +1200,21 @@ __global__ void __launch_bounds__(256) wo_image_kernel(const bf16_t* __restrict_
   }
 }
 
+// the depthwise-tap image of the conv stage's phase 2a: block j < CS_NP writes
+// tap pair j of every channel with the rounding phase 2a applied per launch
+// before (pack_bf16x2), block CS_NP the biases
+__global__ void __launch_bounds__(CS_D) dw_image_kernel(const float* __restrict__ wc, const float* __restrict__ bc,
+                                                        int K, uint32_t* __restrict__ img) {
+  const int j = blockIdx.x, c = threadIdx.x;
+  if (j == CS_NP) {
+    img[j * CS_D + c] = __float_as_uint(bc ? bc[c] : 0.f);
+    return;
+  }
+  const float lo = 2 * j < K ? wc[2 * j * CS_D + c] : 0.f;
+  const float hi = 2 * j + 1 < K ? wc[(2 * j + 1) * CS_D + c] : 0.f;
+  img[j * CS_D + c] = pack_bf16x2(lo, hi);
+}
+
 // ---- the weight-stream image.  Tile s (256 rows x 64 k, 32 KB) in the order
 // ffn_kernel streams them: per FFN block (A, then B for a chain) and hidden
 // chunk c of 256 units: K1 = D / 64 tiles of W1 rows c*256.. (k over D), then
@@ -1467,26 +1482,42 @@ SBK_API int sbk_wo_image(const void* wo, int D, void* img, void* stream) {
   return 0;
 }
 
+// The depthwise taps wc (K, D) fp32, tap-major, and the conv bias bc (D) or
+// null as the conv stage's phase 2a reads them: 16 rows of D packed bf16 tap
+// pairs (taps 2j, 2j + 1; taps >= K are zero), then a row of D fp32 biases
+// (zero for a null bc), sbk_dw_image_elems(D) 32-bit words in all.
+// sbk_conv_ffn_chain / sbk_conv_ffn_tail take this image as their `dwimg`.
+SBK_API long long sbk_dw_image_elems(int D) { return D == CS_D ? (long long)CS_DW_WORDS : -1; }
+
+SBK_API int sbk_dw_image(const float* wc, const float* bc, int K, int D, void* img, void* stream) {
+  if (D != CS_D || K < 1 || K > CS_KMAX || !wc || !img || wc == img) return SBK_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(img) & 15) return SBK_ERR_ARG;
+  hipLaunchKernelGGL(dw_image_kernel, dim3(CS_NP + 1), dim3(CS_D), 0, (hipStream_t)stream, wc, bc, K,
+                     reinterpret_cast<uint32_t*>(img));
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
 namespace {
 // the convolution-module stage's arguments of sbk_conv_ffn_chain / sbk_conv_ffn_tail, checked
 int conv_stage_args(ConvStageArgs& c, const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D,
                     int d_eff, const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg,
-                    long long cimg_elems, const float* cb1p, const float* wc, const float* bc, int K, int causal,
+                    long long cimg_elems, const float* cb1p, const void* dwimg, int K, int causal,
                     const float* cln1_w, const float* cln1_b, float ceps1, const float* cb2, const unsigned char* kpm,
                     const void* out) {
   if (B <= 0 || T <= 0 || (long long)B * T > 0x7fffffffLL || D != CS_D || K < 1 || K > CS_KMAX || !x || !out ||
       x == out || d_eff <= 0 || d_eff > D)
     return SBK_ERR_ARG;
-  if (!o || !wo || !cln0_w || !cln0_b || !cimg || !cb1p || !wc || !cln1_w || !cln1_b) return SBK_ERR_ARG;
+  if (!o || !wo || !cln0_w || !cln0_b || !cimg || !cb1p || !dwimg || !cln1_w || !cln1_b) return SBK_ERR_ARG;
   if (cimg_elems != sbk_conv_image_elems(D)) return SBK_ERR_ARG;
   if ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(wo) | reinterpret_cast<uintptr_t>(bo) |
        reinterpret_cast<uintptr_t>(cln0_w) | reinterpret_cast<uintptr_t>(cln0_b) | reinterpret_cast<uintptr_t>(cimg) |
-       reinterpret_cast<uintptr_t>(cb1p) | reinterpret_cast<uintptr_t>(cln1_w) | reinterpret_cast<uintptr_t>(cln1_b) |
+       reinterpret_cast<uintptr_t>(cb1p) | reinterpret_cast<uintptr_t>(dwimg) | reinterpret_cast<uintptr_t>(cln1_w) | reinterpret_cast<uintptr_t>(cln1_b) |
        reinterpret_cast<uintptr_t>(cb2)) & 15)
     return SBK_ERR_ARG;
   c.x = x; c.B = B; c.T = T; c.K = K; c.padL = causal ? K - 1 : (K - 1) / 2;
   c.g0 = cln0_w; c.b0 = cln0_b; c.eps0 = ceps0;
-  c.img = reinterpret_cast<const bf16_t*>(cimg); c.b1 = cb1p; c.wc = wc; c.bc = bc;
+  c.img = reinterpret_cast<const bf16_t*>(cimg); c.b1 = cb1p; c.dw = reinterpret_cast<const uint32_t*>(dwimg);
   c.g1 = cln1_w; c.b1n = cln1_b; c.eps1 = ceps1;
   c.b2 = cb2; c.kpm = reinterpret_cast<const uint8_t*>(kpm);
   c.o = reinterpret_cast<const bf16_t*>(o); c.wo = reinterpret_cast<const bf16_t*>(wo); c.bo = bo;
@@ -1501,7 +1532,7 @@ int conv_stage_args(ConvStageArgs& c, const float* x, const void* o, const void*
 // tiles read x for the conv halo); yp (B*T, np) bf16.
 SBK_API int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D,
                                int d_eff, const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg,
-                               long long cimg_elems, const float* cb1p, const float* wc, const float* bc, int K,
+                               long long cimg_elems, const float* cb1p, const void* dwimg, const float* bc, int K,
                                int causal, const float* cln1_w, const float* cln1_b, float ceps1, const float* cb2,
                                const unsigned char* kpm, int H, int act, float slope, const float* g0, const float* b0,
                                float eps0, const float* b1, const float* b2, float alpha, const float* gp,
@@ -1510,7 +1541,7 @@ SBK_API int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, co
                                const float* bn, float epsn, const void* img, long long img_elems, int np, void* yp,
                                void* stream) {
   ConvStageArgs c;
-  if (conv_stage_args(c, x, o, wo, bo, B, T, D, d_eff, cln0_w, cln0_b, ceps0, cimg, cimg_elems, cb1p, wc, bc, K, causal,
+  if (conv_stage_args(c, x, o, wo, bo, B, T, D, d_eff, cln0_w, cln0_b, ceps0, cimg, cimg_elems, cb1p, dwimg, K, causal,
                       cln1_w, cln1_b, ceps1, cb2, kpm, out))
     return SBK_ERR_ARG;
   if (!g0b || !b0b || !b1b || !b2b || !gn || !bn || !yp || np <= 0) return SBK_ERR_ARG;
@@ -1545,14 +1576,14 @@ SBK_API int sbk_conv_ffn_chain(const float* x, const void* o, const void* wo, co
 // not alias x.  img = sbk_ffn_image(w1, w2) of one block, no projection.
 SBK_API int sbk_conv_ffn_tail(const float* x, const void* o, const void* wo, const float* bo, int B, int T, int D,
                               int d_eff, const float* cln0_w, const float* cln0_b, float ceps0, const void* cimg,
-                              long long cimg_elems, const float* cb1p, const float* wc, const float* bc, int K,
+                              long long cimg_elems, const float* cb1p, const void* dwimg, const float* bc, int K,
                               int causal, const float* cln1_w, const float* cln1_b, float ceps1, const float* cb2,
                               const unsigned char* kpm, int H, int act, float slope, const float* g0, const float* b0,
                               float eps0, const float* b1, const float* b2, float alpha, const float* gp,
                               const float* bp, float epsp, const float* gn, const float* bn, float epsn, float* u,
                               const void* img, long long img_elems, void* stream) {
   ConvStageArgs c;
-  if (conv_stage_args(c, x, o, wo, bo, B, T, D, d_eff, cln0_w, cln0_b, ceps0, cimg, cimg_elems, cb1p, wc, bc, K, causal,
+  if (conv_stage_args(c, x, o, wo, bo, B, T, D, d_eff, cln0_w, cln0_b, ceps0, cimg, cimg_elems, cb1p, dwimg, K, causal,
                       cln1_w, cln1_b, ceps1, cb2, kpm, u))
     return SBK_ERR_ARG;
   if (!gn || !bn) return SBK_ERR_ARG;

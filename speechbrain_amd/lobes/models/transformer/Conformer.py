@@ -150,8 +150,11 @@ class ConvolutionModule(nn.Module):
         lin = self.after_conv[2]
         wc = self._wc.get("taps", [self.conv.weight], lambda: self.conv.weight.detach().reshape(
             self.conv.weight.shape[0], -1).t().contiguous())  # (K, d): coalesced tap loads
-        return (self.ln_params(), w1p, b1p, wc, self.conv.bias.detach() if self.conv.bias is not None else None,
-                self.causal, (ln.weight.detach(), ln.bias.detach(), ln.eps), w2,
+        # one tensor object per bias version: _enc.dw_image keys its cache on (taps, bias) and
+        # holds them weakly, so the image of the fused launches lives as long as these two do
+        bc = None if self.conv.bias is None else self._wc.get("cbias", [self.conv.bias],
+                                                              lambda: self.conv.bias.detach())
+        return (self.ln_params(), w1p, b1p, wc, bc, self.causal, (ln.weight.detach(), ln.bias.detach(), ln.eps), w2,
                 lin.bias.detach() if lin.bias is not None else None)
 
     def run_fused(self, x2d, B, T, pad_mask_u8=None, pre=None):
