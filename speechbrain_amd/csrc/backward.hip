@@ -717,16 +717,9 @@ __global__ void __launch_bounds__(256) joint_bwd_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------ dropout / residual add
-// Counter-based keep mask: bit-identical for the forward and the backward
-// launch of one (seed, element) pair, independent of grid shape.
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ bool keep_elem(unsigned long long seed, long long i, unsigned thresh) {
-  return (unsigned)(mix64(seed + (unsigned long long)i * 0x9E3779B97F4A7C15ull) >> 40) < thresh;
-}
+// (the keep mask is sbk::Dropout's counter-based hash, sbk_common.h; these
+// two kernels take its fields one by one: behind `alpha` the 8-byte-aligned
+// struct would pad the argument block)
 
 // out = res + alpha * rowmask0(drop(x)); drop(x) = keep ? x / (1 - p) : 0.
 // The backward of this op is the same launch on dy with res = null.
@@ -734,10 +727,10 @@ __global__ void dropout_add_kernel(const void* __restrict__ x, int x_bf16, const
                                    long long rows, int cols, const unsigned char* __restrict__ rowmask, float alpha,
                                    unsigned thresh, float inv_keep, unsigned long long seed, int use_drop,
                                    void* __restrict__ out, int out_bf16) {
+  const sbk::Dropout drop(thresh, inv_keep, seed, use_drop);
   const long long n = rows * cols;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    float v = ldv(x, i, x_bf16) * alpha;
-    if (use_drop) v = keep_elem(seed, i, thresh) ? v * inv_keep : 0.f;
+    float v = drop.apply(i, ldv(x, i, x_bf16) * alpha);
     if (rowmask && rowmask[i / cols]) v = 0.f;
     if (res) v += res[i];
     stv(out, i, v, out_bf16);
@@ -750,14 +743,15 @@ __global__ void dropout_add4_kernel(const void* __restrict__ x, int x_bf16, cons
                                     long long rows, int cols, const unsigned char* __restrict__ rowmask, float alpha,
                                     unsigned thresh, float inv_keep, unsigned long long seed, int use_drop,
                                     void* __restrict__ out, int out_bf16) {
+  const sbk::Dropout drop(thresh, inv_keep, seed, use_drop);
   const long long n4 = rows * cols / 4;
   for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (long long)gridDim.x * blockDim.x) {
     const long long i = 4 * q;
     float4 v = ld4(x, i, x_bf16);
     float e[4] = {v.x * alpha, v.y * alpha, v.z * alpha, v.w * alpha};
-    if (use_drop) {
+    if (drop.use) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = keep_elem(seed, i + k, thresh) ? e[k] * inv_keep : 0.f;
+      for (int k = 0; k < 4; ++k) e[k] = drop.apply(i + k, e[k]);
     }
     if (rowmask && rowmask[i / cols]) e[0] = e[1] = e[2] = e[3] = 0.f;
     if (res) {
@@ -868,8 +862,7 @@ __global__ void __launch_bounds__(256) attn_pkT_kernel(const void* __restrict__ 
 // of Pd and dS are zero.
 __global__ void __launch_bounds__(256) relpos_softmax_bwd_pad_kernel(
     const float* __restrict__ P, const void* __restrict__ dP, float scale, int B, int H, int T, int Tp, int Wp,
-    unsigned thresh, float inv_keep, unsigned long long seed, int use_drop, void* __restrict__ dS,
-    void* __restrict__ Pd, void* __restrict__ dBD, int bf) {
+    sbk::Dropout drop, void* __restrict__ dS, void* __restrict__ Pd, void* __restrict__ dBD, int bf) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long long)B * H * Tp) return;  // whole wave; no barrier below
   const int lane = threadIdx.x & 63;
@@ -885,9 +878,7 @@ __global__ void __launch_bounds__(256) relpos_softmax_bwd_pad_kernel(
   }
   const long long pi = (bh * T + i) * T;  // P row; the dropout index base
   const float* pr = P + pi;
-  auto dscale = [&](int j) __attribute__((always_inline)) {
-    return use_drop ? (keep_elem(seed, pi + j, thresh) ? inv_keep : 0.f) : 1.f;
-  };
+  auto dscale = [&](int j) __attribute__((always_inline)) { return drop.apply(pi + j, 1.f); };
   float s = 0.f;
   for (int j = lane; j < T; j += 64) s += pr[j] * dscale(j) * ldv(dP, so + j, bf);
   s = wave_sum_v(s);
@@ -916,9 +907,8 @@ __global__ void __launch_bounds__(256) relpos_softmax_bwd_pad_kernel(
 // the module's returned weights; may be null) and the same values over the
 // padded rows (B*H, Tp, Tp) in the compute dtype — the A operand of
 // drop(P) V on sbk_gemm_batched.  Same mask as sbk_dropout_add on P.
-__global__ void attn_probs_pad_kernel(const float* __restrict__ P, long long BH, int T, int Tp, unsigned thresh,
-                                      float inv_keep, unsigned long long seed, int use_drop, float* __restrict__ attn,
-                                      void* __restrict__ Pd, int bf) {
+__global__ void attn_probs_pad_kernel(const float* __restrict__ P, long long BH, int T, int Tp, sbk::Dropout drop,
+                                      float* __restrict__ attn, void* __restrict__ Pd, int bf) {
   const long long n = BH * Tp * Tp;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
     const int j = (int)(e % Tp);
@@ -928,8 +918,7 @@ __global__ void attn_probs_pad_kernel(const float* __restrict__ P, long long BH,
     float v = 0.f;
     if (i < T && j < T) {
       const long long idx = (bh * T + i) * T + j;
-      v = P[idx];
-      if (use_drop) v = keep_elem(seed, idx, thresh) ? v * inv_keep : 0.f;
+      v = drop.apply(idx, P[idx]);
       if (attn) attn[idx] = v;
     }
     stv(Pd, e, v, bf);
@@ -1017,11 +1006,6 @@ SBK_API int sbk_attn_dqkv(const float* dq_ac, const float* dq_bd, const float* d
   return 0;
 }
 
-static unsigned drop_thresh(float p) {
-  const double keep = 1.0 - (double)p;
-  return (unsigned)std::min(keep * 16777216.0, 16777216.0);
-}
-
 // Forward attention dropout on the probabilities: attn (fp32, may be null)
 // and Pd over padded rows (B*H, Tp, Tp) in the compute dtype.  p = 0: Pd = P.
 SBK_API int sbk_attn_probs_pad(const float* P, int BH, int T, int Tp, float p, unsigned long long seed, float* attn,
@@ -1029,7 +1013,7 @@ SBK_API int sbk_attn_probs_pad(const float* P, int BH, int T, int Tp, float p, u
   if (BH <= 0 || T <= 0 || Tp < T || !(p >= 0.f) || p >= 1.f) return SBK_ERR_ARG;
   const long long n = (long long)BH * Tp * Tp;
   attn_probs_pad_kernel<<<grid_for(n, 256), 256, 0, (hipStream_t)stream>>>(
-      P, BH, T, Tp, drop_thresh(p), (float)(1.0 / (1.0 - (double)p)), seed, p > 0.f, attn, Pd, pd_bf16);
+      P, BH, T, Tp, sbk::Dropout(p, seed), attn, Pd, pd_bf16);
   SBK_CHECK_LAUNCH();
   return 0;
 }
@@ -1039,16 +1023,15 @@ SBK_API int sbk_dropout_add(const void* x, int x_bf16, const float* res, long lo
                             int out_bf16, void* stream) {
   if (rows < 0 || cols <= 0 || !(p >= 0.f) || p >= 1.f) return SBK_ERR_ARG;
   if (rows == 0) return 0;
-  const double keep = 1.0 - (double)p;
-  const unsigned thresh = (unsigned)std::min(keep * 16777216.0, 16777216.0);
+  const sbk::Dropout drop(p, seed);
   if (vec4_ok(rows, cols, 1, {x, res, out})) {
     dropout_add4_kernel<<<grid_for(rows * cols / 4, 256), 256, 0, (hipStream_t)stream>>>(
-        x, x_bf16, res, rows, cols, rowmask, alpha, thresh, (float)(1.0 / keep), seed, p > 0.f, out, out_bf16);
+        x, x_bf16, res, rows, cols, rowmask, alpha, drop.thresh, drop.inv_keep, drop.seed, drop.use, out, out_bf16);
     SBK_CHECK_LAUNCH();
     return 0;
   }
   dropout_add_kernel<<<grid_for(rows * cols, 256), 256, 0, (hipStream_t)stream>>>(
-      x, x_bf16, res, rows, cols, rowmask, alpha, thresh, (float)(1.0 / keep), seed, p > 0.f, out, out_bf16);
+      x, x_bf16, res, rows, cols, rowmask, alpha, drop.thresh, drop.inv_keep, drop.seed, drop.use, out, out_bf16);
   SBK_CHECK_LAUNCH();
   return 0;
 }
@@ -1215,8 +1198,7 @@ SBK_API int sbk_relpos_softmax_bwd_pad(int dtype_bf16, const float* P, const voi
   if (B <= 0 || H <= 0 || T <= 0 || Tp < T || Wp < 2 * T - 1 || !(p >= 0.f) || p >= 1.f) return SBK_ERR_ARG;
   const long long nrows = (long long)B * H * Tp;
   relpos_softmax_bwd_pad_kernel<<<(unsigned)((nrows + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-      P, dP, scale, B, H, T, Tp, Wp, drop_thresh(p), (float)(1.0 / (1.0 - (double)p)), seed, p > 0.f, dS, Pd, dBD,
-      dtype_bf16);
+      P, dP, scale, B, H, T, Tp, Wp, sbk::Dropout(p, seed), dS, Pd, dBD, dtype_bf16);
   SBK_CHECK_LAUNCH();
   return 0;
 }

@@ -155,6 +155,38 @@ __device__ __forceinline__ uint8_t length_mask_byte(float rel_len, int t, int T)
   return (float)t > floorf(rel_len * (float)T) ? 1 : 0;
 }
 
+// Counter-based dropout keep mask: a function of (seed, element index) alone,
+// so the forward and the backward launch of one op regenerate the same bits
+// whatever their grid shapes.  Every dropout in the library goes through it.
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ bool keep_elem(unsigned long long seed, long long i, unsigned thresh) {
+  return (unsigned)(mix64(seed + (unsigned long long)i * 0x9E3779B97F4A7C15ull) >> 40) < thresh;
+}
+// keep probability 1 - p as a threshold on the 24 hash bits keep_elem compares
+inline unsigned drop_thresh(float p) {
+  const double keep = 1.0 - (double)p;
+  return (unsigned)(keep * 16777216.0 < 16777216.0 ? keep * 16777216.0 : 16777216.0);
+}
+// One dropout of probability p, passed to kernels by value: apply(i, x) is
+// element i of drop(x) = keep ? x / (1 - p) : 0 (x itself when p == 0).
+struct Dropout {
+  unsigned thresh;
+  float inv_keep;
+  unsigned long long seed;
+  int use;
+  Dropout(float p, unsigned long long seed_)
+      : thresh(drop_thresh(p)), inv_keep((float)(1.0 / (1.0 - (double)p))), seed(seed_), use(p > 0.f) {}
+  __host__ __device__ Dropout(unsigned thresh_, float inv_keep_, unsigned long long seed_, int use_)
+      : thresh(thresh_), inv_keep(inv_keep_), seed(seed_), use(use_) {}
+  __device__ __forceinline__ float apply(long long i, float x) const {
+    return use ? (keep_elem(seed, i, thresh) ? x * inv_keep : 0.f) : x;
+  }
+};
+
 // Block-wide sum for blockDim.x a multiple of 64 (<= 1024). `red` >= 16 floats.
 // Block-wide max (all threads get the result); red: >= blockDim/64 floats.
 __device__ __forceinline__ float block_max(float v, float* red) {

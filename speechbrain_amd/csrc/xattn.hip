@@ -7,8 +7,17 @@
 //
 // Not on the encoder's hot path (every Conformer call site is
 // self-attention, which runs in the fused flash kernel of attention.hip), so
-// these kernels are plain fp32 VALU: one workgroup per (query row | key row
-// | band column, head, batch), the row of scores in LDS.  What they must get
+// these kernels are plain fp32 VALU.  The per-row kernels take one workgroup
+// per (query row | key row | band column, head, batch), the row of scores in
+// LDS; they serve any shape and alignment.  The blocked kernels (*_qb_kernel:
+// 16 rows per workgroup, the other operand through LDS in chunks of 64 rows,
+// thread (row, sub) of 16 threads per row) are assembled from one set of tile
+// primitives, each defined once below: xq_stage_rows (global rows -> padded
+// LDS rows), dot4 (a thread's four scores of a chunk), fma8 / acc8_rows (its
+// eight output dims), store8 (their guarded store) and row16_max / row16_sum
+// (the reductions over a row's 16 threads).  Every kernel's dynamic-LDS
+// carve-up is one *_lds() layout that the kernel and its launch both read,
+// and every dropout is sbk::Dropout.  What the kernels must get
 // right is the rel_shift of a non-square band: output (i, j) of the
 // reference's pad / view / drop-row trick is flat element
 // p = i*P + j + q_len of the left-padded (q_len, P+1) band, i.e. row
@@ -34,6 +43,7 @@
 namespace {
 
 using sbk::bf16_to_f32;
+using sbk::Dropout;
 using sbk::f32_to_bf16;
 
 constexpr int kThreads = 256;
@@ -43,15 +53,21 @@ __device__ __forceinline__ float ld(const uint16_t* p, long long i) { return bf1
 __device__ __forceinline__ void st(float* p, long long i, float v) { p[i] = v; }
 __device__ __forceinline__ void st(uint16_t* p, long long i, float v) { p[i] = f32_to_bf16(v); }
 
-// counter-based dropout keep mask (the hash of backward.hip's dropout:
-// forward and backward launches regenerate the same bits)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ bool keep_elem(unsigned long long seed, long long i, unsigned thresh) {
-  return (unsigned)(mix64(seed + (unsigned long long)i * 0x9E3779B97F4A7C15ull) >> 40) < thresh;
+// Dynamic-LDS layout of a kernel: N consecutive float arrays, array i at
+// sm + off[i].  Each kernel's layout is one function next to it; the kernel
+// carves its pointers from it and the host sizes the launch from it.
+template <int N>
+struct Lds {
+  int off[N + 1];
+  __host__ __device__ size_t bytes() const { return (size_t)off[N] * sizeof(float); }
+};
+template <typename... S>
+__host__ __device__ __forceinline__ Lds<sizeof...(S)> lds_of(S... floats) {
+  Lds<sizeof...(S)> l{};
+  int i = 0, n = 0;
+  ((l.off[i++] = n, n += floats), ...);
+  l.off[i] = n;
+  return l;
 }
 
 __device__ float block_reduce(float v, float* red, bool is_max) {
@@ -92,18 +108,22 @@ __device__ __forceinline__ void shift_src(int i, int j, int Lq, int P, int mpf, 
   if (mpf && j - i > P - Lq) c = -1;
 }
 
+// forward and backward row pass, per row: s | qu | red | part, g | dor | red | part
+__host__ __device__ inline Lds<4> row_lds(int Lk, int dh) { return lds_of(Lk, dh, 64, 256); }
+
 template <typename TI>
 __global__ __launch_bounds__(kThreads) void xattn_fwd_kernel(
     const TI* __restrict__ q, int ldq, const TI* __restrict__ k, int ldk, const TI* __restrict__ v, int ldv,
-    const TI* __restrict__ pk, int ldp, int P, const float* __restrict__ pbu, const float* __restrict__ pbv,
+    const TI* __restrict__ pk, int ldp, int P, const float* __restrict__ pbu, const float* __restrict__ pbv, int mpf,
     const unsigned char* __restrict__ kpm, const float* __restrict__ am, long long am_sb, long long am_sh, int Lq,
-    int Lk, int H, int dh, float scale, int mpf, unsigned thresh, float inv_keep, unsigned long long seed,
-    int use_drop, TI* __restrict__ out, int ldo, float* __restrict__ probs, float* __restrict__ attn) {
+    int Lk, int H, int dh, float scale, Dropout drop, TI* __restrict__ out, int ldo, float* __restrict__ probs,
+    float* __restrict__ attn) {
   extern __shared__ float sm[];
-  float* s = sm;             // Lk scores -> probabilities (dropped)
-  float* qu = s + Lk;        // q_i + u
-  float* red = qu + dh;      // 64
-  float* part = red + 64;    // 256
+  const auto L = row_lds(Lk, dh);
+  float* s = sm + L.off[0];     // Lk scores -> probabilities (dropped)
+  float* qu = sm + L.off[1];    // q_i + u
+  float* red = sm + L.off[2];   // 64
+  float* part = sm + L.off[3];  // 256
   const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const TI* qrow = q + (long long)(b * Lq + i) * ldq + h * dh;
   for (int d = threadIdx.x; d < dh; d += kThreads) qu[d] = ld(qrow, d) + (pbu ? pbu[h * dh + d] : 0.f);
@@ -141,11 +161,8 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_kernel(
   for (int j = threadIdx.x; j < Lk; j += kThreads) {
     const float pv = s[j] * inv;
     probs[prow + j] = pv;
-    float pd = pv;
-    if (use_drop) {
-      pd = keep_elem(seed, prow + j, thresh) ? pv * inv_keep : 0.f;
-      attn[prow + j] = pd;
-    }
+    const float pd = drop.apply(prow + j, pv);
+    if (drop.use) attn[prow + j] = pd;
     s[j] = pd;
   }
   __syncthreads();
@@ -154,18 +171,19 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_kernel(
                 [&](int d, float y) { st(orow, d, y); });
 }
 
-// No-position forward (pk == nullptr), query-blocked: one workgroup per
-// (QB query rows, head, batch).  The per-row kernel above gives every
-// score its own thread and walks a key row dimension by dimension, so a
-// wave reads 64 different rows element-wise and every query row re-reads
+// ---------------------------------------------------------------- blocked
+// One workgroup per (XQ_QB rows, head, batch).  The per-row kernels give
+// every score its own thread and walk a key row dimension by dimension, so
+// a wave reads 64 different rows element-wise and every query row re-reads
 // all of K and V (decoder cross-attention over 376 keys: 1.2-2x torch's
-// GEMM-based MHA, profiles/r06u_mha_decoder_timing.log).  Here K and V pass
-// through LDS in chunks of XQ_KC rows, read once per QB query rows with
-// coalesced loads, the scores of the block stay in LDS (QB x Lk) for the
-// softmax, and P·V accumulates per (row, 8 output dims); the LDS rows are
-// padded to dh + 4 floats so the dot products read 16 B at a time, the 16
-// key rows of a lane group 4 banks apart.  fp32 VALU as above (exact fp32
-// operands for the parity path).
+// GEMM-based MHA, profiles/r06u_mha_decoder_timing.log).  Here the other
+// operand passes through LDS in chunks of XQ_KC rows, read once per XQ_QB
+// rows with coalesced loads, and thread (ri, sub) = (tid / 16, tid % 16)
+// owns row ri: in a score step the chunk rows sub + 16 m, in an output step
+// the dims 8 sub .. 8 sub + 7.  The LDS rows are padded to DP = dh + 4 floats
+// so the dot products read 16 B at a time, the 16 chunk rows of a lane group
+// 4 banks apart.  fp32 VALU as above (exact fp32 operands for the parity
+// path).  The tile steps, each written once:
 constexpr int XQ_QB = 16, XQ_KC = 64, XQ_DMAX = 128, XQ_LKMAX = 1024;
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -174,13 +192,17 @@ __device__ __forceinline__ float4 ld4(const uint16_t* p) {
   return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
                      __uint_as_float(u.y & 0xffff0000u));
 }
-// ROWS x dh of src (row stride ld_src elements, 4-element aligned) -> dst
-// (row stride ld_dst floats); rows >= rmax -> 0.  Every load of the thread
-// is issued before the first LDS store (a load -> store loop per element
-// paid the global latency once per element: the first version of these
-// kernels spent most of its time there).
+
+// Stage: rows row0 .. row0 + ROWS - 1 of src (row stride ld_src elements,
+// 4-element aligned) -> dst (row stride ld_dst floats); rows outside
+// [0, rows_total) -> 0 (one unsigned compare: a signed two-sided bound cost
+// 50-160 instructions per kernel).  Every load of the thread is issued
+// before the first LDS store (a load -> store loop per element paid the
+// global latency once per element: the first version of these kernels spent
+// most of its time there).
 template <int ROWS, typename TI>
-__device__ __forceinline__ void xq_stage(float* dst, int ld_dst, const TI* src, long long ld_src, int rmax, int dh) {
+__device__ __forceinline__ void xq_stage_rows(float* dst, int ld_dst, const TI* src, long long ld_src, int row0,
+                                              int rows_total, int dh) {
   constexpr int PT = (ROWS * (XQ_DMAX / 4) + kThreads - 1) / kThreads;  // float4 per thread at dh = XQ_DMAX
   const int q4 = dh >> 2, total = ROWS * q4;
   float4 v[PT];
@@ -189,8 +211,8 @@ __device__ __forceinline__ void xq_stage(float* dst, int ld_dst, const TI* src, 
     const int e = threadIdx.x + u * kThreads;
     v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (e < total) {
-      const int r = e / q4, c = (e - r * q4) * 4;
-      if (r < rmax) v[u] = ld4(src + (long long)r * ld_src + c);
+      const int r = e / q4, c = (e - r * q4) * 4, gr = row0 + r;
+      if ((unsigned)gr < (unsigned)rows_total) v[u] = ld4(src + (long long)gr * ld_src + c);
     }
   }
 #pragma unroll
@@ -202,7 +224,58 @@ __device__ __forceinline__ void xq_stage(float* dst, int ld_dst, const TI* src, 
     }
   }
 }
+// the first rmax rows of src (src already at its first row)
+template <int ROWS, typename TI>
+__device__ __forceinline__ void xq_stage(float* dst, int ld_dst, const TI* src, long long ld_src, int rmax, int dh) {
+  xq_stage_rows<ROWS>(dst, ld_dst, src, ld_src, 0, rmax, dh);
+}
 
+// Four dots, one float4 step: acc[m] += x · T[row(m)] over the four dims at
+// T (the staged tile, already offset to the step's dim; rows DP apart).
+template <typename R>
+__device__ __forceinline__ void dot4(float (&acc)[XQ_KC / 16], const float4 x, const float* T, int DP, R row) {
+#pragma unroll
+  for (int m = 0; m < XQ_KC / 16; ++m) {
+    const float4 t = ld4(T + row(m) * DP);
+    acc[m] += x.x * t.x + x.y * t.y + x.z * t.z + x.w * t.w;
+  }
+}
+
+// Eight dims of one row: acc[0..8) += w * x[0..8).
+__device__ __forceinline__ void fma8(float (&acc)[8], float w, const float* x) {
+  const float4 a = ld4(x), b = ld4(x + 4);
+  acc[0] += w * a.x; acc[1] += w * a.y; acc[2] += w * a.z; acc[3] += w * a.w;
+  acc[4] += w * b.x; acc[5] += w * b.y; acc[6] += w * b.z; acc[7] += w * b.w;
+}
+// ... of the n rows of a staged tile: acc += sum_r w[r] * X[r][0..8) (X
+// already offset to the thread's first dim; rows DP apart).
+__device__ __forceinline__ void acc8_rows(float (&acc)[8], const float* w, const float* X, int DP, int n) {
+  for (int r = 0; r < n; ++r) fma8(acc, w[r], X + r * DP);
+}
+
+// fn(d, acc[d - d0]) for the thread's dims d0 <= d < min(d0 + 8, dh)
+template <typename F>
+__device__ __forceinline__ void store8(const float (&acc)[8], int d0, int dh, F fn) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (d0 + e < dh) fn(d0 + e, acc[e]);
+}
+
+// max / sum over the 16 threads of a row (lanes 16 ri .. 16 ri + 15 of one wave)
+__device__ __forceinline__ float row16_max(float v) {
+#pragma unroll
+  for (int o = 8; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
+  return v;
+}
+__device__ __forceinline__ float row16_sum(float v) {
+#pragma unroll
+  for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o, 16);
+  return v;
+}
+
+// Forward, query-blocked: the scores of the block stay in LDS (QB x Lk) for
+// the softmax, and P·V accumulates per (row, 8 output dims).
+//
 // POS: the rel-pos band term as well.  Output (i, j) takes band element
 // (r, c) = shift_src(i, j); for the common r == i it is (q_i + v)·pk_c with
 // c = j - i + Lq - 1, so the (QB + KC - 1) band rows a block-chunk needs are
@@ -210,30 +283,10 @@ __device__ __forceinline__ void xq_stage(float* dst, int ld_dst, const TI* src, 
 // reference's rel_shift (r > i: q_len > k_len) read global memory.
 constexpr int XQ_BR = XQ_QB + XQ_KC;  // staged band rows per chunk (79 used)
 
-template <int ROWS, typename TI>
-__device__ __forceinline__ void xq_stage_rows(float* dst, int ld_dst, const TI* src, long long ld_src, int row0,
-                                              int rows_total, int dh) {
-  // rows row0 .. row0 + ROWS - 1 of src (rows outside [0, rows_total) -> 0)
-  constexpr int PT = (ROWS * (XQ_DMAX / 4) + kThreads - 1) / kThreads;
-  const int q4 = dh >> 2, total = ROWS * q4;
-  float4 v[PT];
-#pragma unroll
-  for (int u = 0; u < PT; ++u) {
-    const int e = threadIdx.x + u * kThreads;
-    v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (e < total) {
-      const int r = e / q4, c = (e - r * q4) * 4, gr = row0 + r;
-      if (gr >= 0 && gr < rows_total) v[u] = ld4(src + (long long)gr * ld_src + c);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < PT; ++u) {
-    const int e = threadIdx.x + u * kThreads;
-    if (e < total) {
-      const int r = e / q4, c = (e - r * q4) * 4;
-      *reinterpret_cast<float4*>(dst + r * ld_dst + c) = v[u];
-    }
-  }
+// qs | kv | qv (POS) | band (POS) | s
+__host__ __device__ inline Lds<5> fwd_qb_lds(int dh, int Lk, bool pos) {
+  const int DP = dh + 4;
+  return lds_of(XQ_QB * DP, XQ_KC * DP, pos ? XQ_QB * DP : 0, pos ? XQ_BR * DP : 0, XQ_QB * Lk);
 }
 
 template <typename TI, bool POS>
@@ -241,15 +294,16 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_qb_kernel(
     const TI* __restrict__ q, int ldq, const TI* __restrict__ k, int ldk, const TI* __restrict__ v, int ldv,
     const TI* __restrict__ pk, int ldp, int P, const float* __restrict__ pbu, const float* __restrict__ pbv, int mpf,
     const unsigned char* __restrict__ kpm, const float* __restrict__ am, long long am_sb, long long am_sh, int Lq,
-    int Lk, int H, int dh, float scale, unsigned thresh, float inv_keep, unsigned long long seed, int use_drop,
-    TI* __restrict__ out, int ldo, float* __restrict__ probs, float* __restrict__ attn) {
+    int Lk, int H, int dh, float scale, Dropout drop, TI* __restrict__ out, int ldo, float* __restrict__ probs,
+    float* __restrict__ attn) {
   extern __shared__ float sm[];
-  const int DP = dh + 4;                   // padded LDS row (floats): 16-B aligned, rows 4 banks apart
-  float* qs = sm;                          // XQ_QB x DP (POS: q + u)
-  float* kv = qs + XQ_QB * DP;             // XQ_KC x DP (K chunk, then V chunk)
-  float* qv = kv + XQ_KC * DP;             // POS: XQ_QB x DP, q + v
-  float* band = qv + (POS ? XQ_QB * DP : 0);  // POS: XQ_BR x DP band rows from c_base
-  float* s = band + (POS ? XQ_BR * DP : 0);   // XQ_QB x Lk scores -> probabilities (dropped)
+  const int DP = dh + 4;  // padded LDS row (floats): 16-B aligned, rows 4 banks apart
+  const auto L = fwd_qb_lds(dh, Lk, POS);
+  float* qs = sm + L.off[0];    // XQ_QB x DP (POS: q + u)
+  float* kv = sm + L.off[1];    // XQ_KC x DP (K chunk, then V chunk)
+  float* qv = sm + L.off[2];    // POS: XQ_QB x DP, q + v
+  float* band = sm + L.off[3];  // POS: XQ_BR x DP band rows from c_base
+  float* s = sm + L.off[4];     // XQ_QB x Lk scores -> probabilities (dropped)
   const int i0 = blockIdx.x * XQ_QB, h = blockIdx.y, b = blockIdx.z;
   const int nq = min(XQ_QB, Lq - i0);
   const int tid = threadIdx.x, ri = tid >> 4, sub = tid & 15;  // row ri, 16 threads per row
@@ -291,18 +345,8 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_qb_kernel(
     const float* qr = qs + ri * DP;
     const float* vr = qv + ri * DP;
     for (int d = 0; d < dh; d += 4) {
-      const float4 qd = *reinterpret_cast<const float4*>(qr + d);
-      float4 vd;
-      if constexpr (POS) vd = *reinterpret_cast<const float4*>(vr + d);
-#pragma unroll
-      for (int m = 0; m < XQ_KC / 16; ++m) {
-        const float4 kd = *reinterpret_cast<const float4*>(kv + (sub + 16 * m) * DP + d);
-        ac[m] += qd.x * kd.x + qd.y * kd.y + qd.z * kd.z + qd.w * kd.w;
-        if constexpr (POS) {
-          const float4 pd = *reinterpret_cast<const float4*>(band + max(bro[m], 0) * DP + d);
-          bd[m] += vd.x * pd.x + vd.y * pd.y + vd.z * pd.z + vd.w * pd.w;
-        }
-      }
+      dot4(ac, ld4(qr + d), kv + d, DP, [&](int m) { return sub + 16 * m; });
+      if constexpr (POS) dot4(bd, ld4(vr + d), band + d, DP, [&](int m) { return max(bro[m], 0); });
     }
     if constexpr (POS) {
 #pragma unroll
@@ -329,19 +373,17 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_qb_kernel(
     }
   }
   __syncthreads();
-  // softmax per row: 16 threads per row (lanes 16 ri' .. of one wave), xor shuffles within the 16
+  // softmax per row
   float mx = -INFINITY;
   for (int j = sub; j < Lk; j += 16) mx = fmaxf(mx, s[ri * Lk + j]);
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
+  mx = row16_max(mx);
   float sum = 0.f;
   for (int j = sub; j < Lk; j += 16) {
     const float e = expf(s[ri * Lk + j] - mx);  // all -inf: NaN, as the reference's softmax
     s[ri * Lk + j] = e;
     sum += e;
   }
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 16);
+  sum = row16_sum(sum);
   const float inv = 1.f / sum;
   const long long prow = (((long long)b * H + h) * Lq + i0 + ri) * Lk;
   for (int j = sub; j < Lk; j += 16) {
@@ -349,10 +391,8 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_qb_kernel(
     float pd = pv;
     if (ri < nq) {
       probs[prow + j] = pv;
-      if (use_drop) {
-        pd = keep_elem(seed, prow + j, thresh) ? pv * inv_keep : 0.f;
-        attn[prow + j] = pd;
-      }
+      pd = drop.apply(prow + j, pv);
+      if (drop.use) attn[prow + j] = pd;
     }
     s[ri * Lk + j] = pd;
   }
@@ -364,20 +404,11 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_qb_kernel(
     __syncthreads();
     xq_stage<XQ_KC>(kv, DP, v + (long long)(b * Lk + j0) * ldv + h * dh, ldv, nk, dh);
     __syncthreads();
-    if (d0 < dh)
-      for (int jj = 0; jj < nk; ++jj) {
-        const float pj = s[ri * Lk + j0 + jj];
-        const float4 va = *reinterpret_cast<const float4*>(kv + jj * DP + d0);
-        const float4 vb = *reinterpret_cast<const float4*>(kv + jj * DP + d0 + 4);
-        acc[0] += pj * va.x; acc[1] += pj * va.y; acc[2] += pj * va.z; acc[3] += pj * va.w;
-        acc[4] += pj * vb.x; acc[5] += pj * vb.y; acc[6] += pj * vb.z; acc[7] += pj * vb.w;
-      }
+    if (d0 < dh) acc8_rows(acc, s + ri * Lk + j0, kv + d0, DP, nk);
   }
   if (ri < nq && d0 < dh) {
     TI* orow = out + (long long)(b * Lq + i0 + ri) * ldo + h * dh;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (d0 + e < dh) st(orow, d0 + e, acc[e]);
+    store8(acc, d0, dh, [&](int d, float y) { st(orow, d, y); });
   }
 }
 
@@ -387,13 +418,14 @@ __global__ __launch_bounds__(kThreads) void xattn_fwd_qb_kernel(
 template <typename TI>
 __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_kernel(
     const TI* __restrict__ k, int ldk, const TI* __restrict__ v, int ldv, const TI* __restrict__ dO, int lddo,
-    const float* __restrict__ probs, int Lq, int Lk, int H, int dh, float scale, unsigned thresh, float inv_keep,
-    unsigned long long seed, int use_drop, float* __restrict__ G, float* __restrict__ dqu) {
+    const float* __restrict__ probs, int Lq, int Lk, int H, int dh, float scale, Dropout drop,
+    float* __restrict__ G, float* __restrict__ dqu) {
   extern __shared__ float sm[];
-  float* g = sm;           // Lk
-  float* dor = g + Lk;     // dh
-  float* red = dor + dh;   // 64
-  float* part = red + 64;  // 256
+  const auto L = row_lds(Lk, dh);
+  float* g = sm + L.off[0];     // Lk
+  float* dor = sm + L.off[1];   // dh
+  float* red = sm + L.off[2];   // 64
+  float* part = sm + L.off[3];  // 256
   const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const TI* drow = dO + (long long)(b * Lq + i) * lddo + h * dh;
   for (int d = threadIdx.x; d < dh; d += kThreads) dor[d] = ld(drow, d);
@@ -404,7 +436,7 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_kernel(
     const TI* vrow = v + (long long)(b * Lk + j) * ldv + h * dh;
     float dp = 0.f;
     for (int d = 0; d < dh; ++d) dp += dor[d] * ld(vrow, d);
-    if (use_drop) dp = keep_elem(seed, prow + j, thresh) ? dp * inv_keep : 0.f;
+    dp = drop.apply(prow + j, dp);
     g[j] = dp;
     dot += probs[prow + j] * dp;
   }
@@ -419,19 +451,25 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_kernel(
   weighted_rows(g, k + (long long)b * Lk * ldk + h * dh, ldk, Lk, dh, part, [&](int d, float y) { dq[d] = y; });
 }
 
+// ds | kv | g
+__host__ __device__ inline Lds<3> bwd_rows_qb_lds(int dh, int Lk) {
+  return lds_of(XQ_QB * (dh + 4), XQ_KC * (dh + 4), XQ_QB * Lk);
+}
+
 // No-position backward row pass, query-blocked like xattn_fwd_qb_kernel:
 // dP = dO·Vᵀ over V chunks in LDS, G = P ⊙ (dP - Σ P dP) · scale (written
 // to global for the key-row pass), dq = G·K over K chunks in LDS.
 template <typename TI>
 __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_qb_kernel(
     const TI* __restrict__ k, int ldk, const TI* __restrict__ v, int ldv, const TI* __restrict__ dO, int lddo,
-    const float* __restrict__ probs, int Lq, int Lk, int H, int dh, float scale, unsigned thresh, float inv_keep,
-    unsigned long long seed, int use_drop, float* __restrict__ G, float* __restrict__ dq) {
+    const float* __restrict__ probs, int Lq, int Lk, int H, int dh, float scale, Dropout drop,
+    float* __restrict__ G, float* __restrict__ dq) {
   extern __shared__ float sm[];
   const int DP = dh + 4;
-  float* ds = sm;                          // XQ_QB x DP: dO rows
-  float* kv = ds + XQ_QB * DP;             // XQ_KC x DP: V chunk, then K chunk
-  float* g = kv + XQ_KC * DP;              // XQ_QB x Lk: dP, then G
+  const auto L = bwd_rows_qb_lds(dh, Lk);
+  float* ds = sm + L.off[0];  // XQ_QB x DP: dO rows
+  float* kv = sm + L.off[1];  // XQ_KC x DP: V chunk, then K chunk
+  float* g = sm + L.off[2];   // XQ_QB x Lk: dP, then G
   const int i0 = blockIdx.x * XQ_QB, h = blockIdx.y, b = blockIdx.z;
   const int nq = min(XQ_QB, Lq - i0);
   const int tid = threadIdx.x, ri = tid >> 4, sub = tid & 15;
@@ -444,20 +482,13 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_qb_kernel(
     __syncthreads();
     float dp[XQ_KC / 16] = {};
     const float* dr = ds + ri * DP;
-    for (int d = 0; d < dh; d += 4) {
-      const float4 od = *reinterpret_cast<const float4*>(dr + d);
-#pragma unroll
-      for (int m = 0; m < XQ_KC / 16; ++m) {
-        const float4 vd = *reinterpret_cast<const float4*>(kv + (sub + 16 * m) * DP + d);
-        dp[m] += od.x * vd.x + od.y * vd.y + od.z * vd.z + od.w * vd.w;
-      }
-    }
+    for (int d = 0; d < dh; d += 4) dot4(dp, ld4(dr + d), kv + d, DP, [&](int m) { return sub + 16 * m; });
 #pragma unroll
     for (int m = 0; m < XQ_KC / 16; ++m) {
       const int j = j0 + sub + 16 * m;
       if (j >= Lk) continue;
       float x = dp[m];
-      if (use_drop && ri < nq) x = keep_elem(seed, prow + j, thresh) ? x * inv_keep : 0.f;
+      if (ri < nq) x = drop.apply(prow + j, x);
       g[ri * Lk + j] = x;
     }
   }
@@ -465,8 +496,7 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_qb_kernel(
   float dot = 0.f;
   if (ri < nq)
     for (int j = sub; j < Lk; j += 16) dot += probs[prow + j] * g[ri * Lk + j];
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1) dot += __shfl_xor(dot, o, 16);
+  dot = row16_sum(dot);
   for (int j = sub; j < Lk; j += 16) {
     float gv = 0.f;
     if (ri < nq) {
@@ -482,20 +512,11 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_rows_qb_kernel(
     __syncthreads();
     xq_stage<XQ_KC>(kv, DP, k + (long long)(b * Lk + j0) * ldk + h * dh, ldk, nk, dh);
     __syncthreads();
-    if (d0 < dh)
-      for (int jj = 0; jj < nk; ++jj) {
-        const float gj = g[ri * Lk + j0 + jj];
-        const float4 ka = *reinterpret_cast<const float4*>(kv + jj * DP + d0);
-        const float4 kb = *reinterpret_cast<const float4*>(kv + jj * DP + d0 + 4);
-        acc[0] += gj * ka.x; acc[1] += gj * ka.y; acc[2] += gj * ka.z; acc[3] += gj * ka.w;
-        acc[4] += gj * kb.x; acc[5] += gj * kb.y; acc[6] += gj * kb.z; acc[7] += gj * kb.w;
-      }
+    if (d0 < dh) acc8_rows(acc, g + ri * Lk + j0, kv + d0, DP, nk);
   }
   if (ri < nq && d0 < dh) {
     float* dqr = dq + (long long)(b * Lq + i0 + ri) * H * dh + h * dh;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (d0 + e < dh) dqr[d0 + e] = acc[e];
+    store8(acc, d0, dh, [&](int d, float y) { dqr[d] = y; });
   }
 }
 
@@ -510,14 +531,18 @@ __device__ __forceinline__ float dband(const float* Gbh, int r, int c, int Lq, i
   return Gbh[(long long)i * Lk + j];
 }
 
+// w | part
+__host__ __device__ inline Lds<2> bwd_qv_lds(int P) { return lds_of(P, 256); }
+
 // Backward, band-row pass: dq_bd[r] = Σ_c dBD[r][c] pk[c]; dq = dq_ac + dq_bd.
 template <typename TI>
 __global__ __launch_bounds__(kThreads) void xattn_bwd_qv_kernel(
     const TI* __restrict__ pk, int ldp, int P, const float* __restrict__ G, const float* __restrict__ dqu, int Lq,
     int Lk, int H, int dh, int mpf, float* __restrict__ dqv, float* __restrict__ dq) {
   extern __shared__ float sm[];
-  float* w = sm;          // P
-  float* part = w + P;    // 256
+  const auto L = bwd_qv_lds(P);
+  float* w = sm + L.off[0];     // P
+  float* part = sm + L.off[1];  // 256
   const int r = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const float* Gbh = G + ((long long)b * H + h) * Lq * Lk;
   for (int c = threadIdx.x; c < P; c += kThreads) w[c] = dband(Gbh, r, c, Lq, Lk, P, mpf);
@@ -529,25 +554,27 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_qv_kernel(
   });
 }
 
+// gc | pc | part
+__host__ __device__ inline Lds<3> bwd_kv_lds(int Lq) { return lds_of(Lq, Lq, 256); }
+
 // Backward, key-row pass: dk[j] = Σ_i G[i][j] (q_i + u), dv[j] = Σ_i Pd[i][j] dO_i.
 template <typename TI>
 __global__ __launch_bounds__(kThreads) void xattn_bwd_kv_kernel(
     const TI* __restrict__ q, int ldq, const TI* __restrict__ dO, int lddo, const float* __restrict__ pbu,
-    const float* __restrict__ probs, const float* __restrict__ G, int Lq, int Lk, int H, int dh, unsigned thresh,
-    float inv_keep, unsigned long long seed, int use_drop, float* __restrict__ dk, float* __restrict__ dv) {
+    const float* __restrict__ probs, const float* __restrict__ G, int Lq, int Lk, int H, int dh, Dropout drop,
+    float* __restrict__ dk, float* __restrict__ dv) {
   extern __shared__ float sm[];
-  float* gc = sm;          // Lq: G[:, j]
-  float* pc = gc + Lq;     // Lq: Pd[:, j]
-  float* part = pc + Lq;   // 256
+  const auto L = bwd_kv_lds(Lq);
+  float* gc = sm + L.off[0];    // Lq: G[:, j]
+  float* pc = sm + L.off[1];    // Lq: Pd[:, j]
+  float* part = sm + L.off[2];  // 256
   const int j = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const long long base = ((long long)b * H + h) * Lq * Lk + j;
   float gsum = 0.f;
   for (int i = threadIdx.x; i < Lq; i += kThreads) {
     const long long e = base + (long long)i * Lk;
     gc[i] = G[e];
-    float p = probs[e];
-    if (use_drop) p = keep_elem(seed, e, thresh) ? p * inv_keep : 0.f;
-    pc[i] = p;
+    pc[i] = drop.apply(e, probs[e]);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < Lq; i += kThreads) gsum += gc[i];
@@ -562,6 +589,11 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_kv_kernel(
                 [&](int d, float y) { dv[o + d] = y; });
 }
 
+// gs | ps | qs | os
+__host__ __device__ inline Lds<4> bwd_kv_qb_lds(int dh) {
+  return lds_of(XQ_KC * XQ_QB, XQ_KC * XQ_QB, XQ_KC * (dh + 4), XQ_KC * (dh + 4));
+}
+
 // Key-row pass, key-blocked (dh <= XQ_DMAX): one workgroup per (XQ_QB key
 // rows, head, batch) walks the query rows in chunks of XQ_KC: the G / P
 // column slices of its keys (16 consecutive floats of each row) and the q /
@@ -571,14 +603,15 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_kv_kernel(
 template <typename TI>
 __global__ __launch_bounds__(kThreads) void xattn_bwd_kv_qb_kernel(
     const TI* __restrict__ q, int ldq, const TI* __restrict__ dO, int lddo, const float* __restrict__ pbu,
-    const float* __restrict__ probs, const float* __restrict__ G, int Lq, int Lk, int H, int dh, unsigned thresh,
-    float inv_keep, unsigned long long seed, int use_drop, float* __restrict__ dk, float* __restrict__ dv) {
+    const float* __restrict__ probs, const float* __restrict__ G, int Lq, int Lk, int H, int dh, Dropout drop,
+    float* __restrict__ dk, float* __restrict__ dv) {
   extern __shared__ float sm[];
   const int DP = dh + 4;
-  float* gs = sm;                    // XQ_KC x XQ_QB: G[i][j0 + jj]
-  float* ps = gs + XQ_KC * XQ_QB;    // XQ_KC x XQ_QB: Pd
-  float* qs = ps + XQ_KC * XQ_QB;    // XQ_KC x DP: q rows
-  float* os = qs + XQ_KC * DP;       // XQ_KC x DP: dO rows
+  const auto L = bwd_kv_qb_lds(dh);
+  float* gs = sm + L.off[0];  // XQ_KC x XQ_QB: G[i][j0 + jj]
+  float* ps = sm + L.off[1];  // XQ_KC x XQ_QB: Pd
+  float* qs = sm + L.off[2];  // XQ_KC x DP: q rows
+  float* os = sm + L.off[3];  // XQ_KC x DP: dO rows
   const int j0 = blockIdx.x * XQ_QB, h = blockIdx.y, b = blockIdx.z;
   const int nj = min(XQ_QB, Lk - j0);
   const int tid = threadIdx.x, rj = tid >> 4, sub = tid & 15, d0 = 8 * sub;
@@ -594,8 +627,7 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_kv_qb_kernel(
       if (ii < ni && jj < nj) {
         const long long x = gbase + (long long)(i0 + ii) * Lk + jj;
         gv = G[x];
-        pv = probs[x];
-        if (use_drop) pv = keep_elem(seed, x, thresh) ? pv * inv_keep : 0.f;
+        pv = drop.apply(x, probs[x]);
       }
       gs[e] = gv;
       ps[e] = pv;
@@ -604,29 +636,22 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_kv_qb_kernel(
     xq_stage<XQ_KC>(os, DP, dO + (long long)(b * Lq + i0) * lddo + h * dh, lddo, ni, dh);
     __syncthreads();
     if (d0 < dh)
-      for (int ii = 0; ii < ni; ++ii) {
+      for (int ii = 0; ii < ni; ++ii) {  // acc8_rows for dk and dv in one walk (and gsum)
         const float gj = gs[ii * XQ_QB + rj], pj = ps[ii * XQ_QB + rj];
         gsum += gj;
-        const float4 qa = *reinterpret_cast<const float4*>(qs + ii * DP + d0);
-        const float4 qb = *reinterpret_cast<const float4*>(qs + ii * DP + d0 + 4);
-        const float4 oa = *reinterpret_cast<const float4*>(os + ii * DP + d0);
-        const float4 ob = *reinterpret_cast<const float4*>(os + ii * DP + d0 + 4);
-        adk[0] += gj * qa.x; adk[1] += gj * qa.y; adk[2] += gj * qa.z; adk[3] += gj * qa.w;
-        adk[4] += gj * qb.x; adk[5] += gj * qb.y; adk[6] += gj * qb.z; adk[7] += gj * qb.w;
-        adv[0] += pj * oa.x; adv[1] += pj * oa.y; adv[2] += pj * oa.z; adv[3] += pj * oa.w;
-        adv[4] += pj * ob.x; adv[5] += pj * ob.y; adv[6] += pj * ob.z; adv[7] += pj * ob.w;
+        fma8(adk, gj, qs + ii * DP + d0);
+        fma8(adv, pj, os + ii * DP + d0);
       }
   }
   if (rj < nj && d0 < dh) {
     const long long o = (long long)(b * Lk + j0 + rj) * H * dh + h * dh;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (d0 + e < dh) {
-        dk[o + d0 + e] = adk[e] + (pbu ? pbu[h * dh + d0 + e] * gsum : 0.f);
-        dv[o + d0 + e] = adv[e];
-      }
+    store8(adk, d0, dh, [&](int d, float y) { dk[o + d] = y + (pbu ? pbu[h * dh + d] * gsum : 0.f); });
+    store8(adv, d0, dh, [&](int d, float y) { dv[o + d] = y; });
   }
 }
+
+// ps | w
+__host__ __device__ inline Lds<2> bwd_qv_qb_lds(int dh) { return lds_of(XQ_KC * (dh + 4), XQ_QB * XQ_KC); }
 
 // Band-row pass, blocked (dh <= XQ_DMAX, 16-B aligned pk): one workgroup
 // per (XQ_QB band rows, head, batch) walks the band in chunks of XQ_KC
@@ -639,8 +664,9 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_qv_qb_kernel(
     int Lk, int H, int dh, int mpf, float* __restrict__ dqv, float* __restrict__ dq) {
   extern __shared__ float sm[];
   const int DP = dh + 4;
-  float* ps = sm;                      // XQ_KC x DP: pk rows of the chunk
-  float* w = ps + XQ_KC * DP;          // XQ_QB x XQ_KC: dBD of the chunk
+  const auto L = bwd_qv_qb_lds(dh);
+  float* ps = sm + L.off[0];  // XQ_KC x DP: pk rows of the chunk
+  float* w = sm + L.off[1];   // XQ_QB x XQ_KC: dBD of the chunk
   const int r0 = blockIdx.x * XQ_QB, h = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, ri = tid >> 4, sub = tid & 15, d0 = 8 * sub;
   const float* Gbh = G + ((long long)b * H + h) * Lq * Lk;
@@ -654,25 +680,19 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_qv_qb_kernel(
       w[e] = (r0 + rr < Lq && cc < nc) ? dband(Gbh, r0 + rr, c0 + cc, Lq, Lk, P, mpf) : 0.f;
     }
     __syncthreads();
-    if (d0 < dh)
-      for (int cc = 0; cc < nc; ++cc) {
-        const float wc = w[ri * XQ_KC + cc];
-        const float4 pa = *reinterpret_cast<const float4*>(ps + cc * DP + d0);
-        const float4 pb = *reinterpret_cast<const float4*>(ps + cc * DP + d0 + 4);
-        acc[0] += wc * pa.x; acc[1] += wc * pa.y; acc[2] += wc * pa.z; acc[3] += wc * pa.w;
-        acc[4] += wc * pb.x; acc[5] += wc * pb.y; acc[6] += wc * pb.z; acc[7] += wc * pb.w;
-      }
+    if (d0 < dh) acc8_rows(acc, w + ri * XQ_KC, ps + d0, DP, nc);
   }
   if (r0 + ri < Lq && d0 < dh) {
     const long long o = (long long)(b * Lq + r0 + ri) * H * dh + h * dh;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (d0 + e < dh) {
-        dqv[o + d0 + e] = acc[e];
-        dq[o + d0 + e] = dqu[o + d0 + e] + acc[e];
-      }
+    store8(acc, d0, dh, [&](int d, float y) {
+      dqv[o + d] = y;
+      dq[o + d] = dqu[o + d] + y;
+    });
   }
 }
+
+// w | part | red
+__host__ __device__ inline Lds<3> bwd_pk_lds(int Lq) { return lds_of(Lq, 256, 64); }
 
 // Backward, band-column pass: dpk[c] = Σ_b Σ_r dBD[b][r][c] (q_r + v).
 template <typename TI>
@@ -680,9 +700,10 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_pk_kernel(
     const TI* __restrict__ q, int ldq, const float* __restrict__ pbv, const float* __restrict__ G, int B, int Lq,
     int Lk, int H, int dh, int P, int mpf, float* __restrict__ dpk) {
   extern __shared__ float sm[];
-  float* w = sm;          // Lq
-  float* part = w + Lq;   // 256
-  float* red = part + 256;
+  const auto L = bwd_pk_lds(Lq);
+  float* w = sm + L.off[0];     // Lq
+  float* part = sm + L.off[1];  // 256
+  float* red = sm + L.off[2];
   const int c = blockIdx.x, h = blockIdx.y;
   const int dl = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int nd = (dh + 63) / 64;
@@ -719,7 +740,8 @@ __global__ __launch_bounds__(kThreads) void xattn_bwd_pk_kernel(
   }
 }
 
-// operands the query-blocked kernels can stage 4 elements at a time
+// ------------------------------------------------------------------- host
+// operands the blocked kernels can stage 4 elements at a time
 template <typename TI>
 bool qb_aligned(std::initializer_list<const void*> ps, std::initializer_list<int> lds, int dh) {
   if (dh > XQ_DMAX || dh % 4) return false;
@@ -730,15 +752,14 @@ bool qb_aligned(std::initializer_list<const void*> ps, std::initializer_list<int
   return true;
 }
 
-unsigned drop_thresh(float p) {
-  const double keep = 1.0 - (double)p;
-  return (unsigned)fmin(keep * 16777216.0, 16777216.0);
-}
-
-template <typename K>
-int prep_lds(K kern, size_t lds) {
+// one launch of kThreads threads with `lds` bytes of dynamic LDS; the
+// arguments convert to the kernel's parameter types (const void* -> const TI*)
+template <typename... KA, typename... A>
+int launch(void (*kern)(KA...), dim3 grid, size_t lds, hipStream_t st, A... args) {
   if (lds > 160 * 1024) return SBK_ERR_ARG;
   if (sbk::lds_optin((const void*)kern, lds) != hipSuccess) return SBK_ERR_ARG;
+  hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, st, static_cast<KA>(args)...);
+  SBK_CHECK_LAUNCH();
   return 0;
 }
 
@@ -747,109 +768,59 @@ bool bad_dims(int B, int Lq, int Lk, int H, int dh, int P) {
          H > 65535 || B > 65535 || P > 65535 * 2;
 }
 
+// the validated arguments of the two entry points, in the order of their C signatures
+struct FwdArgs {
+  const void *q; int ldq; const void* k; int ldk; const void* v; int ldv; const void* pk; int ldp, P;
+  const float *pbu, *pbv; const unsigned char* kpm; const float* am; long long am_sb, am_sh;
+  int B, Lq, Lk, H, dh; float scale; int mpf; float p; unsigned long long seed;
+  void* out; int ldo; float *probs, *attn; hipStream_t st;
+};
+struct BwdArgs {
+  const void *q; int ldq; const void* k; int ldk; const void* v; int ldv; const void* pk; int ldp, P;
+  const float *pbu, *pbv, *probs; const void* dO; int lddo, B, Lq, Lk, H, dh; float scale; int mpf; float p;
+  unsigned long long seed; float *G, *dqu, *dqv, *dq, *dk, *dv, *dpk; hipStream_t st;
+};
+
 template <typename TI>
-int xattn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* pk, int ldp, int P,
-              const float* pbu, const float* pbv, const unsigned char* kpm, const float* am, long long am_sb,
-              long long am_sh, int B, int Lq, int Lk, int H, int dh, float scale, int mpf, float p,
-              unsigned long long seed, void* out, int ldo, float* probs, float* attn, hipStream_t st) {
-  const int use_drop = p > 0.f;
-  if (use_drop && !attn) return SBK_ERR_ARG;
-  const size_t lq = (size_t)((XQ_QB + XQ_KC + (pk ? XQ_QB + XQ_BR : 0)) * (dh + 4) + XQ_QB * Lk) * sizeof(float);
-  if (Lk <= XQ_LKMAX && lq <= 160 * 1024 &&
-      (pk ? qb_aligned<TI>({q, k, v, pk}, {ldq, ldk, ldv, ldp}, dh) : qb_aligned<TI>({q, k, v}, {ldq, ldk, ldv}, dh))) {
-    const dim3 grid((Lq + XQ_QB - 1) / XQ_QB, H, B);
-    const unsigned th = drop_thresh(p);
-    const float ik = (float)(1.0 / (1.0 - (double)p));
-    if (pk) {
-      auto kq = xattn_fwd_qb_kernel<TI, true>;
-      if (int rc = prep_lds(kq, lq)) return rc;
-      hipLaunchKernelGGL(kq, grid, dim3(kThreads), lq, st, (const TI*)q, ldq, (const TI*)k, ldk, (const TI*)v, ldv,
-                         (const TI*)pk, ldp, P, pbu, pbv, mpf, kpm, am, am_sb, am_sh, Lq, Lk, H, dh, scale, th, ik,
-                         seed, use_drop, (TI*)out, ldo, probs, attn);
-    } else {
-      auto kq = xattn_fwd_qb_kernel<TI, false>;
-      if (int rc = prep_lds(kq, lq)) return rc;
-      hipLaunchKernelGGL(kq, grid, dim3(kThreads), lq, st, (const TI*)q, ldq, (const TI*)k, ldk, (const TI*)v, ldv,
-                         (const TI*)nullptr, 0, 0, (const float*)nullptr, (const float*)nullptr, 0, kpm, am, am_sb,
-                         am_sh, Lq, Lk, H, dh, scale, th, ik, seed, use_drop, (TI*)out, ldo, probs, attn);
-    }
-    SBK_CHECK_LAUNCH();
-    return 0;
-  }
-  const size_t lds = (size_t)(Lk + dh + 64 + 256) * sizeof(float);
-  auto kern = xattn_fwd_kernel<TI>;
-  if (int rc = prep_lds(kern, lds)) return rc;
-  hipLaunchKernelGGL(kern, dim3(Lq, H, B), dim3(kThreads), lds, st, (const TI*)q, ldq, (const TI*)k, ldk,
-                     (const TI*)v, ldv, (const TI*)pk, ldp, P, pbu, pbv, kpm, am, am_sb, am_sh, Lq, Lk, H, dh, scale,
-                     mpf, drop_thresh(p), (float)(1.0 / (1.0 - (double)p)), seed, use_drop, (TI*)out, ldo, probs,
-                     attn);
-  SBK_CHECK_LAUNCH();
-  return 0;
+int xattn_fwd(const FwdArgs& a) {
+  const Dropout drop(a.p, a.seed);
+  if (drop.use && !a.attn) return SBK_ERR_ARG;
+  const size_t lq = fwd_qb_lds(a.dh, a.Lk, a.pk != nullptr).bytes();
+  const bool qb = a.Lk <= XQ_LKMAX && lq <= 160 * 1024 &&
+                  (a.pk ? qb_aligned<TI>({a.q, a.k, a.v, a.pk}, {a.ldq, a.ldk, a.ldv, a.ldp}, a.dh)
+                        : qb_aligned<TI>({a.q, a.k, a.v}, {a.ldq, a.ldk, a.ldv}, a.dh));
+  const auto kern = !qb ? xattn_fwd_kernel<TI> : a.pk ? xattn_fwd_qb_kernel<TI, true> : xattn_fwd_qb_kernel<TI, false>;
+  return launch(kern, dim3(qb ? (a.Lq + XQ_QB - 1) / XQ_QB : a.Lq, a.H, a.B), qb ? lq : row_lds(a.Lk, a.dh).bytes(),
+                a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.pk, a.ldp, a.P, a.pbu, a.pbv, a.mpf, a.kpm, a.am, a.am_sb,
+                a.am_sh, a.Lq, a.Lk, a.H, a.dh, a.scale, drop, a.out, a.ldo, a.probs, a.attn);
 }
 
 template <typename TI>
-int xattn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* pk, int ldp, int P,
-              const float* pbu, const float* pbv, const float* probs, const void* dO, int lddo, int B, int Lq, int Lk,
-              int H, int dh, float scale, int mpf, float p, unsigned long long seed, float* G, float* dqu, float* dqv,
-              float* dq, float* dk, float* dv, float* dpk, hipStream_t st) {
-  const unsigned thresh = drop_thresh(p);
-  const float inv_keep = (float)(1.0 / (1.0 - (double)p));
-  const int use_drop = p > 0.f;
-  if (Lk <= XQ_LKMAX && qb_aligned<TI>({k, v, dO}, {ldk, ldv, lddo}, dh)) {
-    const size_t lq = (size_t)((XQ_QB + XQ_KC) * (dh + 4) + XQ_QB * Lk) * sizeof(float);
-    auto kq = xattn_bwd_rows_qb_kernel<TI>;
-    if (int rc = prep_lds(kq, lq)) return rc;
-    hipLaunchKernelGGL(kq, dim3((Lq + XQ_QB - 1) / XQ_QB, H, B), dim3(kThreads), lq, st, (const TI*)k, ldk,
-                       (const TI*)v, ldv, (const TI*)dO, lddo, probs, Lq, Lk, H, dh, scale, thresh, inv_keep, seed,
-                       use_drop, G, pk ? dqu : dq);
-    SBK_CHECK_LAUNCH();
-  } else {
-    const size_t lds = (size_t)(Lk + dh + 64 + 256) * sizeof(float);
-    auto kern = xattn_bwd_rows_kernel<TI>;
-    if (int rc = prep_lds(kern, lds)) return rc;
-    hipLaunchKernelGGL(kern, dim3(Lq, H, B), dim3(kThreads), lds, st, (const TI*)k, ldk, (const TI*)v, ldv,
-                       (const TI*)dO, lddo, probs, Lq, Lk, H, dh, scale, thresh, inv_keep, seed, use_drop, G,
-                       pk ? dqu : dq);
-    SBK_CHECK_LAUNCH();
+int xattn_bwd(const BwdArgs& a) {
+  const Dropout drop(a.p, a.seed);
+  const dim3 per_q(a.Lq, a.H, a.B), blk_q((a.Lq + XQ_QB - 1) / XQ_QB, a.H, a.B);
+  const bool rows_qb = a.Lk <= XQ_LKMAX && qb_aligned<TI>({a.k, a.v, a.dO}, {a.ldk, a.ldv, a.lddo}, a.dh);
+  if (int rc = launch(rows_qb ? xattn_bwd_rows_qb_kernel<TI> : xattn_bwd_rows_kernel<TI>, rows_qb ? blk_q : per_q,
+                      rows_qb ? bwd_rows_qb_lds(a.dh, a.Lk).bytes() : row_lds(a.Lk, a.dh).bytes(), a.st, a.k, a.ldk,
+                      a.v, a.ldv, a.dO, a.lddo, a.probs, a.Lq, a.Lk, a.H, a.dh, a.scale, drop, a.G,
+                      a.pk ? a.dqu : a.dq))
+    return rc;
+  if (a.pk) {
+    const bool qv_qb = qb_aligned<TI>({a.pk}, {a.ldp}, a.dh);
+    if (int rc = launch(qv_qb ? xattn_bwd_qv_qb_kernel<TI> : xattn_bwd_qv_kernel<TI>, qv_qb ? blk_q : per_q,
+                        qv_qb ? bwd_qv_qb_lds(a.dh).bytes() : bwd_qv_lds(a.P).bytes(), a.st, a.pk, a.ldp, a.P, a.G,
+                        a.dqu, a.Lq, a.Lk, a.H, a.dh, a.mpf, a.dqv, a.dq))
+      return rc;
   }
-  if (pk && qb_aligned<TI>({pk}, {ldp}, dh)) {
-    const size_t lq = (size_t)(XQ_KC * (dh + 4) + XQ_QB * XQ_KC) * sizeof(float);
-    auto kq = xattn_bwd_qv_qb_kernel<TI>;
-    if (int rc = prep_lds(kq, lq)) return rc;
-    hipLaunchKernelGGL(kq, dim3((Lq + XQ_QB - 1) / XQ_QB, H, B), dim3(kThreads), lq, st, (const TI*)pk, ldp, P, G,
-                       dqu, Lq, Lk, H, dh, mpf, dqv, dq);
-    SBK_CHECK_LAUNCH();
-  } else if (pk) {
-    const size_t lds = (size_t)(P + 256) * sizeof(float);
-    auto kern = xattn_bwd_qv_kernel<TI>;
-    if (int rc = prep_lds(kern, lds)) return rc;
-    hipLaunchKernelGGL(kern, dim3(Lq, H, B), dim3(kThreads), lds, st, (const TI*)pk, ldp, P, G, dqu, Lq, Lk, H, dh,
-                       mpf, dqv, dq);
-    SBK_CHECK_LAUNCH();
-  }
-  if (qb_aligned<TI>({q, dO}, {ldq, lddo}, dh)) {
-    const size_t lq = (size_t)(2 * XQ_KC * XQ_QB + 2 * XQ_KC * (dh + 4)) * sizeof(float);
-    auto kq = xattn_bwd_kv_qb_kernel<TI>;
-    if (int rc = prep_lds(kq, lq)) return rc;
-    hipLaunchKernelGGL(kq, dim3((Lk + XQ_QB - 1) / XQ_QB, H, B), dim3(kThreads), lq, st, (const TI*)q, ldq,
-                       (const TI*)dO, lddo, pbu, probs, G, Lq, Lk, H, dh, thresh, inv_keep, seed, use_drop, dk, dv);
-    SBK_CHECK_LAUNCH();
-  } else {
-    const size_t lds = (size_t)(2 * Lq + 256) * sizeof(float);
-    auto kern = xattn_bwd_kv_kernel<TI>;
-    if (int rc = prep_lds(kern, lds)) return rc;
-    hipLaunchKernelGGL(kern, dim3(Lk, H, B), dim3(kThreads), lds, st, (const TI*)q, ldq, (const TI*)dO, lddo, pbu,
-                       probs, G, Lq, Lk, H, dh, thresh, inv_keep, seed, use_drop, dk, dv);
-    SBK_CHECK_LAUNCH();
-  }
-  if (pk) {  // (a column-blocked variant over 188 workgroups measured 2x slower: 550 vs 276 us)
-    const size_t lds = (size_t)(Lq + 256 + 64) * sizeof(float);
-    auto kern = xattn_bwd_pk_kernel<TI>;
-    if (int rc = prep_lds(kern, lds)) return rc;
-    hipLaunchKernelGGL(kern, dim3(P, H, 1), dim3(kThreads), lds, st, (const TI*)q, ldq, pbv, G, B, Lq, Lk, H, dh, P,
-                       mpf, dpk);
-    SBK_CHECK_LAUNCH();
-  }
+  const bool kv_qb = qb_aligned<TI>({a.q, a.dO}, {a.ldq, a.lddo}, a.dh);
+  if (int rc = launch(kv_qb ? xattn_bwd_kv_qb_kernel<TI> : xattn_bwd_kv_kernel<TI>,
+                      dim3(kv_qb ? (a.Lk + XQ_QB - 1) / XQ_QB : a.Lk, a.H, a.B),
+                      kv_qb ? bwd_kv_qb_lds(a.dh).bytes() : bwd_kv_lds(a.Lq).bytes(), a.st, a.q, a.ldq, a.dO, a.lddo,
+                      a.pbu, a.probs, a.G, a.Lq, a.Lk, a.H, a.dh, drop, a.dk, a.dv))
+    return rc;
+  if (a.pk)  // (a column-blocked variant over 188 workgroups measured 2x slower: 550 vs 276 us)
+    return launch(xattn_bwd_pk_kernel<TI>, dim3(a.P, a.H, 1), bwd_pk_lds(a.Lq).bytes(), a.st, a.q, a.ldq, a.pbv, a.G,
+                  a.B, a.Lq, a.Lk, a.H, a.dh, a.P, a.mpf, a.dpk);
   return 0;
 }
 
@@ -864,11 +835,9 @@ SBK_API int sbk_relpos_xattn_fwd(int dtype_bf16, const void* q, int ldq, const v
   if (!q || !k || !v || (pk && (!pbu || !pbv || ldp < H * dh)) || !out || !probs || bad_dims(B, Lq, Lk, H, dh, P) ||
       p_drop < 0.f || p_drop >= 1.f || ldq < H * dh || ldk < H * dh || ldv < H * dh || ldo < H * dh)
     return SBK_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype_bf16 ? xattn_fwd<uint16_t>(q, ldq, k, ldk, v, ldv, pk, ldp, P, pbu, pbv, kpm, am, am_sb, am_sh, B, Lq,
-                                          Lk, H, dh, scale, mask_pos_future, p_drop, seed, out, ldo, probs, attn, st)
-                    : xattn_fwd<float>(q, ldq, k, ldk, v, ldv, pk, ldp, P, pbu, pbv, kpm, am, am_sb, am_sh, B, Lq, Lk,
-                                       H, dh, scale, mask_pos_future, p_drop, seed, out, ldo, probs, attn, st);
+  const FwdArgs a{q, ldq, k, ldk, v, ldv, pk, ldp, P, pbu, pbv, kpm, am, am_sb, am_sh, B, Lq, Lk, H, dh, scale,
+                  mask_pos_future, p_drop, seed, out, ldo, probs, attn, (hipStream_t)stream};
+  return dtype_bf16 ? xattn_fwd<uint16_t>(a) : xattn_fwd<float>(a);
 }
 
 SBK_API int sbk_relpos_xattn_bwd(int dtype_bf16, const void* q, int ldq, const void* k, int ldk, const void* v,
@@ -880,9 +849,7 @@ SBK_API int sbk_relpos_xattn_bwd(int dtype_bf16, const void* q, int ldq, const v
       (pk && (!pbu || !pbv || !dqu || !dqv || !dpk || ldp < H * dh)) || bad_dims(B, Lq, Lk, H, dh, P) ||
       p_drop < 0.f || p_drop >= 1.f || ldq < H * dh || ldk < H * dh || ldv < H * dh || lddo < H * dh)
     return SBK_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype_bf16 ? xattn_bwd<uint16_t>(q, ldq, k, ldk, v, ldv, pk, ldp, P, pbu, pbv, probs, dO, lddo, B, Lq, Lk, H,
-                                          dh, scale, mask_pos_future, p_drop, seed, G, dqu, dqv, dq, dk, dv, dpk, st)
-                    : xattn_bwd<float>(q, ldq, k, ldk, v, ldv, pk, ldp, P, pbu, pbv, probs, dO, lddo, B, Lq, Lk, H,
-                                       dh, scale, mask_pos_future, p_drop, seed, G, dqu, dqv, dq, dk, dv, dpk, st);
+  const BwdArgs a{q, ldq, k, ldk, v, ldv, pk, ldp, P, pbu, pbv, probs, dO, lddo, B, Lq, Lk, H, dh, scale,
+                  mask_pos_future, p_drop, seed, G, dqu, dqv, dq, dk, dv, dpk, (hipStream_t)stream};
+  return dtype_bf16 ? xattn_bwd<uint16_t>(a) : xattn_bwd<float>(a);
 }
