@@ -1017,6 +1017,46 @@ int sbk_ligru_bwd(int bf16, int D, int act, const void* uT, const float* hx, con
                   const float* mask, const float* dy, int B, int T, int H, float* dG, float* dhw, float* dhx,
                   void* stream);
 
+/* ------------------------------------------- time-domain augmentation */
+
+/* csrc/tdaug.hip: the waveform stage of the reference's
+ * TimeDomainSpecAugment (processing/speech_augmentation.py:435-1173).  All
+ * waveforms fp32; tables int32 / fp32 device arrays computed by the caller.
+ * Limits (SBK_ERR_ARG beyond them, before any launch): B <= 65535,
+ * L <= 128, L * W <= 2048, S <= 64, T * C and T_out * C within int32. */
+
+/* Output elements one workgroup of these kernels owns. */
+int sbk_tdaug_tile(void);
+
+/* Polyphase resampler: y (B, T_out, C) from x (B, T, C), channels fastest.
+ * first (L), w (L, W): y[k L + i] = sum_j w[i][j] x[first[i] + k M + j], x
+ * zero outside [0, T), j ascending, for every k L + i < T_out. */
+int sbk_resample(const float* x, int B, int T, int C, const int* first, const float* w, int L, int M, int W,
+                 int T_out, float* y, void* stream);
+
+/* y (B, T): y[t] = sum_k taps[k] x[t + k - 50] (a correlation with zero
+ * padding), taps (101), k ascending. */
+int sbk_fir101(const float* x, int B, int T, const float* taps, float* y, void* stream);
+
+/* y (B, T, C) = x with the samples of segs (B, S, 2) [start, end) zeroed
+ * (an empty segment pads a row).  With noise (n_noise uniform draws) segment
+ * j of row b is filled with 2 nm u - nm instead, u = noise[noff[b][j] + t -
+ * start], nm = 2 amp_b noise_factor, amp_b = sum_t |x[b, t]| / lengths[b]
+ * over all T; overlapping segments: the last wins.  That path needs C == 1,
+ * noff (B, S), lengths (B), and the scratch partial (B, 64) and amp (B),
+ * which receives amp_b (a row reduction launched before the fill). */
+int sbk_drop_chunks(const float* x, int B, int T, int C, const int* segs, int S, const int* noff, const float* noise,
+                    long long n_noise, const int* lengths, float noise_factor, float* partial, float* amp, float* y,
+                    void* stream);
+
+/* One launch for resample -> filter -> zero fill of x (B, T) into y
+ * (B, T_out), bit-identical to the three entry points above in sequence
+ * (the filter sees the resampled signal zero-padded, not extrapolated).
+ * first == null: no resample (T_out == T); taps == null: no filter;
+ * S == 0: no segments; none of them: a copy. */
+int sbk_tdaug(const float* x, int B, int T, const int* first, const float* w, int L, int M, int W, int T_out,
+              const float* taps, const int* segs, int S, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,12 @@ SIGNATURES = {
     # augment.hip
     "sbk_specaugment": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _ll, _vp],
     "sbk_specaugment_needs_scratch": [_i, _i, _i, _i, _i, _i, _i, _i],
+    # tdaug.hip (time-domain augmentation: resample, 101-tap filter, chunk fill, the three fused)
+    "sbk_tdaug_tile": [],
+    "sbk_resample": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "sbk_fir101": [_vp, _i, _i, _vp, _vp, _vp],
+    "sbk_drop_chunks": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _ll, _vp, _f, _vp, _vp, _vp, _vp],
+    "sbk_tdaug": [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
     # rnnt.hip
     "sbk_rnnt_forward": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "sbk_rnnt_workspace_floats": [_i, _i, _i],

@@ -7,14 +7,19 @@ bit — also for ROCm tensors, where the reference would draw masks on the
 device generator.  The warp / mask / mean-fill arithmetic runs in
 speechbrain_amd/csrc/augment.hip; the input is mutated in place and
 returned, as in the reference.
+
+TimeDomainSpecAugment (augment.py:204-299) chains the SpeedPerturb, DropFreq
+and DropChunk drop-ins of processing.speech_augmentation; with zero-fill
+chunks its three stages run as one launch of sbk_tdaug.
 """
 from typing import Optional
 
 import torch
 
 from .._lib import OPS, check, custom_op, lib, ptr, require_device, stream_of
+from ..processing.speech_augmentation import DropChunk, DropFreq, SpeedPerturb, _check_wave, _Pinned
 
-__all__ = ["SpecAugment"]
+__all__ = ["SpecAugment", "TimeDomainSpecAugment"]
 
 _WARP_MODES = {"bicubic": 0, "bilinear": 1}
 
@@ -146,3 +151,77 @@ class SpecAugment(torch.nn.Module):
         OPS.specaugment_(x, N, T, F, c, w, fm_d, tm_d, not self.replace_with_zero, -1,
                                    _WARP_MODES.get(self.time_warp_mode, 0))
         return x
+
+
+class TimeDomainSpecAugment(torch.nn.Module):
+    """Speed perturbation, frequency dropping and chunk dropping on the
+    waveform.  `fused` (default True) selects the one-launch path, taken for
+    (batch, time) input and zero-fill chunks; otherwise — white-noise chunks
+    need the filtered signal's amplitude first — the three stages run one
+    after another.  Both make the same draws in the same order."""
+
+    def __init__(self, perturb_prob=1.0, drop_freq_prob=1.0, drop_chunk_prob=1.0, speeds=[95, 100, 105],
+                 sample_rate=16000, drop_freq_count_low=0, drop_freq_count_high=3, drop_chunk_count_low=0,
+                 drop_chunk_count_high=5, drop_chunk_length_low=1000, drop_chunk_length_high=2000,
+                 drop_chunk_noise_factor=0):
+        super().__init__()
+        self.speed_perturb = SpeedPerturb(perturb_prob=perturb_prob, orig_freq=sample_rate, speeds=speeds)
+        self.drop_freq = DropFreq(drop_prob=drop_freq_prob, drop_count_low=drop_freq_count_low,
+                                  drop_count_high=drop_freq_count_high)
+        self.drop_chunk = DropChunk(drop_prob=drop_chunk_prob, drop_count_low=drop_chunk_count_low,
+                                    drop_count_high=drop_chunk_count_high, drop_length_low=drop_chunk_length_low,
+                                    drop_length_high=drop_chunk_length_high, noise_factor=drop_chunk_noise_factor)
+        self.fused = True
+        self.last_draws = None
+        self._pin = _Pinned()
+
+    def draws(self, T, lengths):
+        """The three stages' host draws for a (batch, T) input, in the
+        reference's order: (resampler or None, T_out, 101 taps or None,
+        (B, S, 2) segments or None).  A stage that is not applied — below
+        its probability, speed 100, zero notches, zero chunks — is None."""
+        sp, df, dc = self.speed_perturb, self.drop_freq, self.drop_chunk
+        sp.last_draws = _, idx = sp.draws()
+        rs = None
+        if idx is not None:
+            sp.samp_index = idx
+            if sp.resamplers[idx].orig_freq != sp.resamplers[idx].new_freq:
+                rs = sp.resamplers[idx]
+                if not hasattr(rs, "first_indices"):
+                    rs._indices_and_weights()
+        T_out = rs._output_samples(T) if rs is not None else T
+        df.last_draws = _, count, _, taps = df.draws()
+        if count is None or int(count) == 0:
+            taps = None
+        # the chunk draws depend on the absolute lengths of the resampled
+        # batch: B values device -> host, as the reference syncs for them
+        lengths_abs = (lengths * T_out).long().cpu()
+        dc.last_draws = _, times, chunks, _ = dc.draws(lengths_abs)
+        segs = dc.segments(chunks, T_out) if times is not None else None
+        return rs, T_out, taps, segs
+
+    def _forward_fused(self, x, lengths):
+        require_device(lengths)
+        rs, T_out, taps, segs = self.draws(x.shape[1], lengths)
+        first = w = taps_d = segs_d = None
+        if rs is not None:
+            first, w = rs.table(x.device)
+        parts = [p for p in (taps, segs) if p is not None]
+        if parts:
+            dev = self._pin.upload(parts, x.device)
+            taps_d = dev[0] if taps is not None else None
+            segs_d = dev[-1] if segs is not None else None
+        return OPS.tdaug(x, first, w, rs.conv_stride if rs is not None else 1, T_out, taps_d, segs_d)
+
+    def forward(self, waveforms, lengths):
+        """Returns the distorted waveforms."""
+        _check_wave(waveforms, "TimeDomainSpecAugment")
+        with torch.no_grad():
+            if self.fused and waveforms.dim() == 2 and not self.drop_chunk.noise_factor:
+                waveforms = self._forward_fused(waveforms, lengths)
+            else:
+                waveforms = self.speed_perturb(waveforms)
+                waveforms = self.drop_freq(waveforms)
+                waveforms = self.drop_chunk(waveforms, lengths)
+        self.last_draws = (self.speed_perturb.last_draws, self.drop_freq.last_draws, self.drop_chunk.last_draws)
+        return waveforms
