@@ -24,19 +24,9 @@ using namespace sbk;
 
 namespace {
 
-enum Act { ACT_NONE = 0, ACT_SWISH = 1, ACT_GLU = 2, ACT_LRELU = 3, ACT_GELU = 4 };
-
-struct Epi {
-  const float* bias;        // [N] (GLU: permuted like W) or null
-  int act;
-  float slope;              // LeakyReLU negative slope
-  const float* res;         // residual [M, ldr] fp32 or null
-  int ldr;
-  float alpha;              // val scale before residual add
-  const uint8_t* rowmask;   // [M]: nonzero -> val = 0
-  void* out;
-  int ldc;
-  int out_bf16;
+// The shared epilogue plus what only these kernels take.  The base comes
+// first and the members keep their order: Epi is a by-value kernel argument.
+struct Epi : GemmEpi {
   // optional row LayerNorm of the stored rows (full-row tiles, BN == N == 256):
   // ln_out = LN(out row; ln_g, ln_b, ln_eps)
   const float* ln_g = nullptr;
@@ -53,15 +43,68 @@ struct Epi {
   int zdiv = 0;
   long long sCo = 0;
 };
+static_assert(sizeof(GemmEpi) == 56 && sizeof(Epi) == 136, "kernel argument layout");
 
-// C tile (fp32, row stride CR, in LDS) -> global through the fused epilogue:
-// bias, activation (GLU pairs [value16 | gate16] column groups), row mask,
-// alpha, fp32 residual; fp32 or bf16 output, 16-/8-B vector stores.
-template <int ACT>
-__device__ __forceinline__ float epi_act(float x, float slope) {
-  if (ACT == ACT_SWISH) return x * (1.0f / (1.0f + __expf(-x)));
-  if (ACT == ACT_LRELU) return x >= 0.f ? x : x * slope;
-  if (ACT == ACT_GELU) return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+// ---- tile steps shared by the three kernels: 4 waves as 2 x 2, wave (wm, wn)
+// owning TM x TN MFMA tiles of 16 x 16 ----
+
+// C tile row stride (floats) of a BN-wide tile in LDS
+constexpr int c_stride(int BN) { return BN + 4; }
+
+// Workgroup -> tile origin.  XCD-aware remap (bijective): workgroups dealt
+// round-robin to the 8 XCDs get consecutive tiles per XCD, so the N-tiles of
+// one A row-panel share an L2.
+template <int BM, int BN>
+__device__ __forceinline__ void tile_origin(int N, int& m0, int& n0) {
+  const int ntn = (N + BN - 1) / BN;
+  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
+  m0 = (tile_id / ntn) * BM;
+  n0 = (tile_id % ntn) * BN;
+}
+
+// acc += fa x fb over one 32-wide K slice
+template <typename T, int TM, int TN>
+__device__ __forceinline__ void mma_tiles(f32x4 (&acc)[TM][TN], const typename MT<T>::frag (&fa)[TM],
+                                          const typename MT<T>::frag (&fb)[TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) MT<T>::mma(acc[i][j], fa[i], fb[j]);
+}
+
+// One BK-deep step on the padded LDS layout (row stride LDSR): as / bs point
+// at this lane's fragment of the wave's first A / W row.
+template <typename T, int TM, int TN, int BK, int LDSR>
+__device__ __forceinline__ void mma_step(f32x4 (&acc)[TM][TN], const T* as, const T* bs) {
+#pragma unroll
+  for (int ks = 0; ks < BK / 32; ++ks) {
+    typename MT<T>::frag fa[TM], fb[TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) fa[i] = MT<T>::load(as + i * 16 * LDSR + ks * 32);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) fb[j] = MT<T>::load(bs + j * 16 * LDSR + ks * 32);
+    mma_tiles<T>(acc, fa, fb);
+  }
+}
+
+// Accumulators -> LDS C tile (16x16 C/D: col fr = lane & 15, row = 4 g + r, g = lane >> 4)
+template <int BM, int BN, int TM, int TN>
+__device__ __forceinline__ void spill_ctile(float* Cs, const f32x4 (&acc)[TM][TN], int wm, int wn, int g, int fr) {
+  constexpr int CR = c_stride(BN), WM = BM / 2, WN = BN / 2;
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Cs[(wm * WM + i * 16 + 4 * g + r) * CR + wn * WN + j * 16 + fr] = acc[i][j][r];
+}
+
+// The activation of both paths of store_ctile (GLU is not one: it pairs
+// columns).  The fast path passes a compile-time act, which folds.
+__device__ __forceinline__ float epi_act(int act, float x, float slope) {
+  if (act == ACT_SWISH) return x * (1.0f / (1.0f + __expf(-x)));
+  if (act == ACT_LRELU) return x >= 0.f ? x : x * slope;
+  if (act == ACT_GELU) return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
   return x;
 }
 
@@ -74,7 +117,7 @@ __device__ __forceinline__ float epi_act(float x, float slope) {
 template <int BM, int BN, int NT, int ACT, bool GLU>
 __device__ __forceinline__ void store_ctile_fast(const float* __restrict__ Cs, const Epi& ep, int m0, int n0,
                                                  int tid) {
-  constexpr int CR = BN + 4;
+  constexpr int CR = c_stride(BN);
   constexpr int NCOL = GLU ? BN / 2 : BN;
   constexpr int QPR = NCOL / 4;          // column quads per row
   static_assert(NT % QPR == 0, "thread map");
@@ -102,7 +145,7 @@ __device__ __forceinline__ void store_ctile_fast(const float* __restrict__ Cs, c
       for (int e = 0; e < 4; ++e) v[e] *= 1.0f / (1.0f + __expf(-gg[e]));
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = epi_act<ACT>(v[e], ep.slope);
+      for (int e = 0; e < 4; ++e) v[e] = epi_act(ACT, v[e], ep.slope);
     }
     const float sc = (ep.rowmask && ep.rowmask[row]) ? 0.f : ep.alpha;
 #pragma unroll
@@ -138,7 +181,7 @@ template <int BM, int BN, int NT>
 __device__ __forceinline__ void store_ctile_rowln(const float* __restrict__ Cs, const Epi& ep, int m0, int M,
                                                   int tid, const float4 (&rres)[BM / 4]) {
   static_assert(BN == 256 && NT == 256, "row-LN epilogue: 256 columns, 4 waves");
-  constexpr int CR = BN + 4, RPW = BM / 4;
+  constexpr int CR = c_stride(BN), RPW = BM / 4;
   const int lane = tid & 63, w = tid >> 6;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   const float4 bs = ep.bias ? *reinterpret_cast<const float4*>(ep.bias + 4 * lane) : z4;
@@ -193,10 +236,14 @@ __device__ __forceinline__ void store_ctile_rowln(const float* __restrict__ Cs, 
   }
 }
 
+// C tile (fp32, row stride CR, in LDS) -> global through the fused epilogue:
+// bias, activation (GLU pairs [value16 | gate16] column groups), row mask,
+// alpha, fp32 residual; fp32 or bf16 output, 16-/8-B vector stores.
+// The fast path when the tile is whole and aligned; else quad by quad, every
+// column bound checked (bias included: nothing past bias[N - 1] is read).
 template <int BM, int BN, int NT>
 __device__ __forceinline__ void store_ctile(const float* __restrict__ Cs, const Epi& ep, int m0, int n0, int M,
                                             int N, int tid) {
-
   if (m0 + BM <= M && n0 + BN <= N && epi_aligned(ep)) {
     switch (ep.act) {
       case ACT_NONE: store_ctile_fast<BM, BN, NT, ACT_NONE, false>(Cs, ep, m0, n0, tid); return;
@@ -206,7 +253,7 @@ __device__ __forceinline__ void store_ctile(const float* __restrict__ Cs, const 
       case ACT_GELU: store_ctile_fast<BM, BN, NT, ACT_GELU, false>(Cs, ep, m0, n0, tid); return;
     }
   }
-  constexpr int CR = BN + 4;
+  constexpr int CR = c_stride(BN);
   const bool glu = ep.act == ACT_GLU;
   const int ncols = glu ? BN / 2 : BN;       // output columns of this tile
   const int oc0 = glu ? n0 / 2 : n0;         // first output column
@@ -232,13 +279,8 @@ __device__ __forceinline__ void store_ctile(const float* __restrict__ Cs, const 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float x = Cs[r * CR + o + e];
-        if (ep.bias) x += ep.bias[n0 + o + e];
-        if (ep.act == ACT_SWISH)
-          x = x * (1.0f / (1.0f + __expf(-x)));
-        else if (ep.act == ACT_LRELU)
-          x = x >= 0.f ? x : x * ep.slope;
-        else if (ep.act == ACT_GELU)
-          x = 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+        if (ep.bias && oc0 + o + e < nout) x += ep.bias[n0 + o + e];  // (a column past N is never stored)
+        x = epi_act(ep.act, x, ep.slope);
         v[e] = x;
       }
     }
@@ -283,6 +325,34 @@ __device__ __forceinline__ void store_ctile(const float* __restrict__ Cs, const 
   }
 }
 
+// One launch as the entry points describe it (host side)
+struct Problem {
+  const void* A;
+  int lda;
+  const void* W;
+  int ldw;
+  int M, N, K;
+  Epi ep;
+  hipStream_t s;
+  int batch = 1;
+};
+
+// The host launcher of all three kernels: dynamic LDS is the larger of the
+// kernel's K staging and the epilogue's C tile, opted in above 64 KB; one
+// workgroup per BM x BN tile, grid.z the batch.
+template <int BM, int BN, typename T>
+int launch_tile(void (*kern)(const T*, int, const T*, int, int, int, int, Epi), size_t staging, const Problem& p) {
+  const size_t ctile = sizeof(float) * BM * c_stride(BN);
+  const size_t lds = staging > ctile ? staging : ctile;
+  if (lds > 64 * 1024)
+    if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(kern), lds)) return (int)e;
+  const int grid = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+  hipLaunchKernelGGL(kern, dim3(grid, 1, p.batch), dim3(256), lds, p.s, reinterpret_cast<const T*>(p.A), p.lda,
+                     reinterpret_cast<const T*>(p.W), p.ldw, p.M, p.N, p.K, p.ep);
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
 template <typename T, int BM, int BN, int BK, int NBUF>
 __global__ void __launch_bounds__(256) gemm_kernel(const T* __restrict__ A, int lda, const T* __restrict__ W,
                                                    int ldw, int M, int N, int K, Epi ep) {
@@ -310,12 +380,8 @@ __global__ void __launch_bounds__(256) gemm_kernel(const T* __restrict__ A, int 
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-  const int ntn = (N + BN - 1) / BN;
-  // XCD-aware remap (bijective): workgroups dealt round-robin to the 8 XCDs get
-  // consecutive tiles per XCD, so the N-tiles of one A row-panel share an L2.
-  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
-  const int m0 = (tile_id / ntn) * BM;
-  const int n0 = (tile_id % ntn) * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(N, m0, n0);
   // full-row (BN == 256) tiles are sbk_gemm_ln's: the residual rows of the
   // row-LN epilogue are fetched here so their latency hides under the K loop
   constexpr bool ROWLN = BN == 256;
@@ -377,18 +443,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(const T* __restrict__ A, int 
     if (kt + 1 < nk) gload((kt + 1) * BK);
     const T* as = As + cur * BM * LDSR + (wm * WM + fr) * LDSR + fk;
     const T* bs = Bs + cur * BN * LDSR + (wn * WN + fr) * LDSR + fk;
-#pragma unroll
-    for (int ks = 0; ks < BK / 32; ++ks) {
-      typename Tr::frag fa[TM], fb[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) fa[i] = Tr::load(as + i * 16 * LDSR + ks * 32);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = Tr::load(bs + j * 16 * LDSR + ks * 32);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) Tr::mma(acc[i][j], fa[i], fb[j]);
-    }
+    mma_step<T, TM, TN, BK, LDSR>(acc, as, bs);
     if (NBUF == 2) {
       if (kt + 1 < nk) sstore(cur ^ 1);
       __syncthreads();
@@ -403,15 +458,8 @@ __global__ void __launch_bounds__(256) gemm_kernel(const T* __restrict__ A, int 
 
   // ---- epilogue: accumulators -> LDS C tile -> coalesced vector pass ----
   // (the staging ring is free: the last loop iteration ended with a barrier)
-  constexpr int CR = BN + 4;  // C tile row stride (floats)
   float* Cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        Cs[(wm * WM + i * 16 + 4 * (lane >> 4) + r) * CR + wn * WN + j * 16 + fr] = acc[i][j][r];
+  spill_ctile<BM, BN>(Cs, acc, wm, wn, lane >> 4, fr);
   __syncthreads();
   if constexpr (ROWLN)
     store_ctile_rowln<BM, BN, 256>(Cs, ep, m0, M, tid, rres);
@@ -420,22 +468,10 @@ __global__ void __launch_bounds__(256) gemm_kernel(const T* __restrict__ A, int 
 }
 
 template <typename T, int BM, int BN, int BK, int NBUF = 2>
-int launch(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epi& ep, hipStream_t s,
-           int batch = 1) {
+int launch(const Problem& p) {
   constexpr int LDSR = BK + (sizeof(T) == 2 ? 2 : 1) * MT<T>::PAD;
-  size_t lds = (size_t)NBUF * (BM + BN) * LDSR * sizeof(T);
-  const size_t cbytes = (size_t)BM * (BN + 4) * 4;  // epilogue C tile
-  if (cbytes > lds) lds = cbytes;
-  if (lds > 64 * 1024)
-    if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&gemm_kernel<T, BM, BN, BK, NBUF>), lds))
-      return (int)e;
-  const int grid = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_kernel<T, BM, BN, BK, NBUF>), dim3(grid, 1, batch), dim3(256), lds, s,
-                     reinterpret_cast<const T*>(A), lda, reinterpret_cast<const T*>(W), ldw, M, N, K, ep);
-  SBK_CHECK_LAUNCH();
-  return 0;
+  return launch_tile<BM, BN>(gemm_kernel<T, BM, BN, BK, NBUF>, (size_t)NBUF * (BM + BN) * LDSR * sizeof(T), p);
 }
-
 
 // LDS-DMA ring GEMM (bf16, K % 64 == 0, K >= 192): 4 waves (2x2), tile BM x BN,
 // 64-deep K steps staged global -> LDS by global_load_lds_dwordx4 (full
@@ -462,10 +498,8 @@ __global__ void __launch_bounds__(256) gemm_ring_kernel(const bf16_t* __restrict
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w >> 1, wn = w & 1;
   const int fr = lane & 15, g = lane >> 4;
-  const int ntn = (N + BN - 1) / BN;
-  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
-  const int m0 = (tile_id / ntn) * BM;
-  const int n0 = (tile_id % ntn) * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(N, m0, n0);
   const int nk = K / BK;
 
   // piece p of a tile covers rows 8p .. 8p+7; lane -> row 8p + lane/8, chunk lane%8
@@ -522,42 +556,23 @@ __global__ void __launch_bounds__(256) gemm_ring_kernel(const bf16_t* __restrict
         const int r = wn * WN + j * 16 + fr;
         fb[j] = *reinterpret_cast<const bf16x8*>(Bs + r * BK + (((ks * 4 + g) ^ ((r >> 1) & 7)) << 3));
       }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+      mma_tiles<bf16_t>(acc, fa, fb);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail re-loads
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  constexpr int CR = BN + 4;
   float* Cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        Cs[(wm * WM + i * 16 + 4 * g + r) * CR + wn * WN + j * 16 + fr] = acc[i][j][r];
+  spill_ctile<BM, BN>(Cs, acc, wm, wn, g, fr);
   __syncthreads();
   store_ctile<BM, BN, NT>(Cs, ep, m0, n0, M, N, tid);
 }
 
 template <int BM, int BN>
-int launch_ring(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epi& ep, hipStream_t s) {
-  size_t lds = (size_t)4 * (BM + BN) * 64 * sizeof(bf16_t);
-  const size_t cbytes = (size_t)BM * (BN + 4) * 4;
-  if (cbytes > lds) lds = cbytes;
-  if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&gemm_ring_kernel<BM, BN>), lds)) return (int)e;
-  const int grid = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_ring_kernel<BM, BN>), dim3(grid), dim3(256), lds, s, reinterpret_cast<const bf16_t*>(A),
-                     lda, reinterpret_cast<const bf16_t*>(W), ldw, M, N, K, ep);
-  SBK_CHECK_LAUNCH();
-  return 0;
+int launch_ring(const Problem& p) {
+  return launch_tile<BM, BN>(gemm_ring_kernel<BM, BN>, (size_t)4 * (BM + BN) * 64 * sizeof(bf16_t), p);
 }
-
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -587,10 +602,8 @@ __global__ void __launch_bounds__(256) gemm_pf_kernel(const bf16_t* __restrict__
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-  const int ntn = (N + BN - 1) / BN;
-  const int tile_id = xcd_tile(gridDim.x, blockIdx.x);
-  const int m0 = (tile_id / ntn) * BM;
-  const int n0 = (tile_id % ntn) * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(N, m0, n0);
   const int nk = (K + BK - 1) / BK;
 
   auto gload = [&](int kt, u32x4 (&rs)[CH]) __attribute__((always_inline)) {
@@ -640,18 +653,7 @@ __global__ void __launch_bounds__(256) gemm_pf_kernel(const bf16_t* __restrict__
     constexpr int u = decltype(U)::value;
     const bf16_t* as = As + (kt & 1) * BM * LDSR + (wm * WM + fr) * LDSR + fk;
     const bf16_t* bs = Bs + (kt & 1) * BN * LDSR + (wn * WN + fr) * LDSR + fk;
-#pragma unroll
-    for (int ks = 0; ks < BK / 32; ++ks) {
-      bf16x8 fa[TM], fb[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(as + i * 16 * LDSR + ks * 32);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(bs + j * 16 * LDSR + ks * 32);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
+    mma_step<bf16_t, TM, TN, BK, LDSR>(acc, as, bs);
     sstore((kt + 1) & 1, sset(IntC<u + 1>{}));   // tile kt+1 (requested 3 steps ago; a dummy past the end)
     gload(min(kt + 4, nk - 1), sset(U));          // this set's tile kt is in LDS already
     __syncthreads();
@@ -663,29 +665,15 @@ __global__ void __launch_bounds__(256) gemm_pf_kernel(const bf16_t* __restrict__
     if (kt0 + 3 < nk) step(kt0 + 3, IntC<3>{});
   }
 
-  constexpr int CR = BN + 4;
   float* Cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        Cs[(wm * WM + i * 16 + 4 * (lane >> 4) + r) * CR + wn * WN + j * 16 + fr] = acc[i][j][r];
+  spill_ctile<BM, BN>(Cs, acc, wm, wn, lane >> 4, fr);
   __syncthreads();
   store_ctile<BM, BN, NT>(Cs, ep, m0, n0, M, N, tid);
 }
 
 template <int BM, int BN, int BK>
-int launch_pf(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epi& ep, hipStream_t s) {
-  size_t lds = (size_t)2 * (BM + BN) * (BK + 16) * sizeof(bf16_t);
-  const size_t cbytes = (size_t)BM * (BN + 4) * 4;
-  if (cbytes > lds) lds = cbytes;
-  const int grid = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_pf_kernel<BM, BN, BK>), dim3(grid), dim3(256), lds, s, reinterpret_cast<const bf16_t*>(A),
-                     lda, reinterpret_cast<const bf16_t*>(W), ldw, M, N, K, ep);
-  SBK_CHECK_LAUNCH();
-  return 0;
+int launch_pf(const Problem& p) {
+  return launch_tile<BM, BN>(gemm_pf_kernel<BM, BN, BK>, (size_t)2 * (BM + BN) * (BK + 16) * sizeof(bf16_t), p);
 }
 
 }  // namespace
@@ -694,8 +682,6 @@ int launch_pf(const void* A, int lda, const void* W, int ldw, int M, int N, int 
 // host asks for it here so weights are permuted consistently.
 SBK_API int sbk_gemm_glu_group(int dtype_bf16) { (void)dtype_bf16; return 16; }  // [value16 | gate16] groups
 
-// dtype_bf16: A and W are bf16 (else fp32).  tile: 0 auto, 1 = 128x128, 2 = 64x64, 3 = 128x64 (BK 64,
-// double-buffered); bf16 only: 4/5/6 = 64x64 / 64x128 / 128x64 with BK 256 single buffer,
 // out = res + alpha * (A @ W^T + bias) (rows masked -> 0 before the residual),
 // then u = LN(out row) — the attention output projection and the convolution
 // module's LayerNorm (Conformer.py:69-72, attention.py:636) in one launch.
@@ -712,23 +698,22 @@ SBK_API int sbk_gemm_ln(int dtype_bf16, const void* A, int lda, const void* W, i
                        reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ln_g) |
                        reinterpret_cast<uintptr_t>(ln_b) | reinterpret_cast<uintptr_t>(u);
   if (al & 15) return SBK_ERR_ARG;
-  Epi ep{bias, ACT_NONE, 0.f, res, ldr, alpha, rowmask, out, ldc, 0};
-  ep.ln_g = ln_g;
-  ep.ln_b = ln_b;
-  ep.ln_eps = ln_eps;
-  ep.ln_out = u;
-  ep.ldu = ldu;
-  ep.ln_bf16 = u_bf16;
-  hipStream_t s = (hipStream_t)stream;
+  const Problem p{A, lda, W, ldw, M, N, K,
+                  Epi{{bias, ACT_NONE, 0.f, res, ldr, alpha, rowmask, out, ldc, 0}, ln_g, ln_b, ln_eps, u, ldu, u_bf16},
+                  (hipStream_t)stream};
+  // tile ids (gemm_kernel, BM x 256 x BK, register double buffer; fp32
+  // operands have the one 32 x 256 x 32):
+  //   bf16  0 = 32 x 256 x 32   1 = 32 x 256 x 64   2 = 64 x 256 x 32
   if (dtype_bf16) {
-    if (tile == 2) return launch<bf16_t, 64, 256, 32, 2>(A, lda, W, ldw, M, N, K, ep, s);
-    if (tile == 1) return launch<bf16_t, 32, 256, 64, 2>(A, lda, W, ldw, M, N, K, ep, s);
-    return launch<bf16_t, 32, 256, 32, 2>(A, lda, W, ldw, M, N, K, ep, s);
+    if (tile == 2) return launch<bf16_t, 64, 256, 32, 2>(p);
+    if (tile == 1) return launch<bf16_t, 32, 256, 64, 2>(p);
+    return launch<bf16_t, 32, 256, 32, 2>(p);
   }
-  return launch<float, 32, 256, 32, 2>(A, lda, W, ldw, M, N, K, ep, s);
+  return launch<float, 32, 256, 32, 2>(p);
 }
 
-// 7 = 128x128 BK 128 single buffer, 8 = 64x64 BK 128 double buffer.
+// dtype_bf16: A and W are bf16 (else fp32).  tile: 0 chooses, else the table
+// above the switch.
 SBK_API int sbk_gemm(int dtype_bf16, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                      const float* bias, int act, float slope, const float* res, int ldr, float alpha,
                      const uint8_t* rowmask, void* out, int ldc, int out_bf16, int tile, void* stream) {
@@ -737,55 +722,84 @@ SBK_API int sbk_gemm(int dtype_bf16, const void* A, int lda, const void* W, int 
   if ((K % vec) || (lda % vec) || (ldw % vec)) return SBK_ERR_ARG;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return SBK_ERR_ARG;
   if (act == ACT_GLU && (N % 32)) return SBK_ERR_ARG;  // whole [a16|gate16] groups
-  Epi ep{bias, act, slope, res, ldr, alpha, rowmask, out, ldc, out_bf16};
   hipStream_t s = (hipStream_t)stream;
+  const Problem p{A, lda, W, ldw, M, N, K, Epi{{bias, act, slope, res, ldr, alpha, rowmask, out, ldc, out_bf16}}, s};
   // tile 30: the 256 x 256 multi-phase kernel (gemm256.hip), N % 256 == 0,
   // K % 64 == 0; taken by default when it fills the chip (>= 180 tiles) at
   // K >= 256 — config 5's projections: 0.97-1.03 PF/s against 0.67-0.82 for
   // the best of the other tiles (profiles/r05c_g256_shapes.log)
   if (dtype_bf16 && (tile == 30 || tile == 0)) {
-    const Gemm256Epi e{bias, act, slope, res, ldr, alpha, rowmask, out, ldc, out_bf16};
-    const bool ok = gemm256_supported(M, N, K, lda, ldw, A, W, e);
+    const bool ok = gemm256_supported(M, N, K, lda, ldw, A, W, p.ep);
     if (tile == 30 && !ok) return SBK_ERR_ARG;
     if (ok && (tile == 30 || (K >= 256 && (long long)((M + 255) / 256) * (N / 256) >= 180)))
-      return gemm256_launch(A, lda, W, ldw, M, N, K, e, s);
+      return gemm256_launch(A, lda, W, ldw, M, N, K, p.ep, s);
   }
   // tile 2 (64x64x64) measured best for every encoder shape (M = B*T = 12032,
   // scripts/kbench.py gemm); the joint-output projection of the transducer
   // (M = B*T*U1 = 782080, N = 1000, K = 1024) runs 1.5x faster on 128x128x128
   // (scripts/logits_gemm_probe.py: 3.69 -> 2.46 ms, 652 TF/s).
   if (tile == 0) tile = (dtype_bf16 && (long long)M * N >= (32LL << 20) && K >= 512 && N >= 256) ? 7 : 2;
+  // Every tile id.  All kernels: 256 threads as 2 x 2 waves; K, lda and ldw
+  // multiples of the 16-B vector (checked above).  An id that is not listed
+  // runs tile 2.
+  //   id  kernel            BM x BN x BK   K buffers                       argument rule
+  //  bf16 operands
+  //    1  gemm_kernel       128x128x 64   2 LDS, register double buffer
+  //    2  gemm_kernel        64x 64x 64   2                               (the default)
+  //    3  gemm_kernel       128x 64x 64   2
+  //    4  gemm_kernel        64x 64x256   1
+  //    5  gemm_kernel        64x128x256   1
+  //    6  gemm_kernel       128x 64x256   1
+  //    7  gemm_kernel       128x128x128   1
+  //    8  gemm_kernel        64x 64x128   2
+  //    9  gemm_kernel        64x 64x 32   2
+  //   10  gemm_kernel       128x 64x 32   2
+  //   11  gemm_ring_kernel  128x128x 64   4-slot LDS-DMA ring             K % 64 == 0, K >= 192
+  //   12  gemm_ring_kernel  128x 64x 64   4-slot LDS-DMA ring             K % 64 == 0, K >= 192
+  //   13  gemm_ring_kernel   64x 64x 64   4-slot LDS-DMA ring             K % 64 == 0, K >= 192
+  //   17  gemm_kernel        64x128x 32   2
+  //   18  gemm_pf_kernel     64x 64x 64   2 LDS, 4 register stages
+  //   19  gemm_pf_kernel    128x 64x 64   2 LDS, 4 register stages
+  //   20  gemm_pf_kernel     64x128x 64   2 LDS, 4 register stages
+  //   21  gemm_pf_kernel    128x128x 64   2 LDS, 4 register stages
+  //   22  gemm_pf_kernel     64x 64x 32   2 LDS, 4 register stages
+  //   30  gemm256_kernel    256x256x 64   2 LDS-DMA (gemm256.hip)         N % 256 == 0, K % 64 == 0, no GLU,
+  //                                                                       16-B aligned bias / res / out
+  //  fp32 operands
+  //    1  gemm_kernel       128x128x 32   2
+  //    2  gemm_kernel        64x 64x 32   2                               (the default)
+  //    3  gemm_kernel       128x 64x 32   2
   if (dtype_bf16) {
     switch (tile) {
-      case 1: return launch<bf16_t, 128, 128, 64>(A, lda, W, ldw, M, N, K, ep, s);
-      case 3: return launch<bf16_t, 128, 64, 64>(A, lda, W, ldw, M, N, K, ep, s);
-      case 4: return launch<bf16_t, 64, 64, 256, 1>(A, lda, W, ldw, M, N, K, ep, s);
-      case 5: return launch<bf16_t, 64, 128, 256, 1>(A, lda, W, ldw, M, N, K, ep, s);
-      case 6: return launch<bf16_t, 128, 64, 256, 1>(A, lda, W, ldw, M, N, K, ep, s);
-      case 7: return launch<bf16_t, 128, 128, 128, 1>(A, lda, W, ldw, M, N, K, ep, s);
-      case 8: return launch<bf16_t, 64, 64, 128, 2>(A, lda, W, ldw, M, N, K, ep, s);
-      case 9: return launch<bf16_t, 64, 64, 32, 2>(A, lda, W, ldw, M, N, K, ep, s);
-      case 10: return launch<bf16_t, 128, 64, 32, 2>(A, lda, W, ldw, M, N, K, ep, s);
-      case 18: return launch_pf<64, 64, 64>(A, lda, W, ldw, M, N, K, ep, s);
-      case 19: return launch_pf<128, 64, 64>(A, lda, W, ldw, M, N, K, ep, s);
-      case 20: return launch_pf<64, 128, 64>(A, lda, W, ldw, M, N, K, ep, s);
-      case 21: return launch_pf<128, 128, 64>(A, lda, W, ldw, M, N, K, ep, s);
-      case 22: return launch_pf<64, 64, 32>(A, lda, W, ldw, M, N, K, ep, s);
-      case 17: return launch<bf16_t, 64, 128, 32, 2>(A, lda, W, ldw, M, N, K, ep, s);
+      case 1: return launch<bf16_t, 128, 128, 64>(p);
+      case 3: return launch<bf16_t, 128, 64, 64>(p);
+      case 4: return launch<bf16_t, 64, 64, 256, 1>(p);
+      case 5: return launch<bf16_t, 64, 128, 256, 1>(p);
+      case 6: return launch<bf16_t, 128, 64, 256, 1>(p);
+      case 7: return launch<bf16_t, 128, 128, 128, 1>(p);
+      case 8: return launch<bf16_t, 64, 64, 128, 2>(p);
+      case 9: return launch<bf16_t, 64, 64, 32, 2>(p);
+      case 10: return launch<bf16_t, 128, 64, 32, 2>(p);
+      case 18: return launch_pf<64, 64, 64>(p);
+      case 19: return launch_pf<128, 64, 64>(p);
+      case 20: return launch_pf<64, 128, 64>(p);
+      case 21: return launch_pf<128, 128, 64>(p);
+      case 22: return launch_pf<64, 64, 32>(p);
+      case 17: return launch<bf16_t, 64, 128, 32, 2>(p);
       case 11: case 12: case 13: {
         // LDS-DMA ring: K % 64 == 0, K >= 192, 16-B aligned rows
         if ((K % 64) || K < 192 || (lda % 8) || (ldw % 8)) return SBK_ERR_ARG;
-        if (tile == 11) return launch_ring<128, 128>(A, lda, W, ldw, M, N, K, ep, s);
-        if (tile == 12) return launch_ring<128, 64>(A, lda, W, ldw, M, N, K, ep, s);
-        return launch_ring<64, 64>(A, lda, W, ldw, M, N, K, ep, s);
+        if (tile == 11) return launch_ring<128, 128>(p);
+        if (tile == 12) return launch_ring<128, 64>(p);
+        return launch_ring<64, 64>(p);
       }
-      default: return launch<bf16_t, 64, 64, 64>(A, lda, W, ldw, M, N, K, ep, s);
+      default: return launch<bf16_t, 64, 64, 64>(p);
     }
   }
   switch (tile) {
-    case 1: return launch<float, 128, 128, 32>(A, lda, W, ldw, M, N, K, ep, s);
-    case 3: return launch<float, 128, 64, 32>(A, lda, W, ldw, M, N, K, ep, s);
-    default: return launch<float, 64, 64, 32>(A, lda, W, ldw, M, N, K, ep, s);
+    case 1: return launch<float, 128, 128, 32>(p);
+    case 3: return launch<float, 128, 64, 32>(p);
+    default: return launch<float, 64, 64, 32>(p);
   }
 }
 
@@ -802,12 +816,10 @@ SBK_API int sbk_gemm_batched(int dtype_bf16, const void* A, int lda, long long s
   const int vec = dtype_bf16 ? 8 : 4;
   if ((K % vec) || (lda % vec) || (ldw % vec) || (sA % vec) || (sW % vec)) return SBK_ERR_ARG;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return SBK_ERR_ARG;
-  Epi ep{nullptr, ACT_NONE, 0.f, nullptr, 0, 1.f, nullptr, out, ldc, out_bf16};
-  ep.sA = sA;
-  ep.sW = sW;
-  ep.sC = sC;
-  ep.zdiv = zdiv;
-  ep.sCo = sCo;
-  if (dtype_bf16) return launch<bf16_t, 64, 64, 64>(A, lda, W, ldw, M, N, K, ep, (hipStream_t)stream, batch);
-  return launch<float, 64, 64, 32>(A, lda, W, ldw, M, N, K, ep, (hipStream_t)stream, batch);
+  const Problem p{A, lda, W, ldw, M, N, K,
+                  Epi{{nullptr, ACT_NONE, 0.f, nullptr, 0, 1.f, nullptr, out, ldc, out_bf16},
+                      nullptr, nullptr, 0.f, nullptr, 0, 0, sA, sW, sC, zdiv, sCo},
+                  (hipStream_t)stream, batch};
+  if (dtype_bf16) return launch<bf16_t, 64, 64, 64>(p);
+  return launch<float, 64, 64, 32>(p);
 }

@@ -43,8 +43,6 @@ using namespace sbk;
 
 namespace {
 
-enum { G_NONE = 0, G_SWISH = 1, G_LRELU = 3, G_GELU = 4 };
-
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -109,10 +107,23 @@ __device__ __forceinline__ f2v gelu_fast2(f2v x) {
 
 template <int ACT>
 __device__ __forceinline__ float act_f(float x, float slope) {
-  if (ACT == G_SWISH) return x * (1.0f / (1.0f + __expf(-x)));
-  if (ACT == G_LRELU) return x >= 0.f ? x : x * slope;
-  if (ACT == G_GELU) return gelu_fast(x);
+  if (ACT == ACT_SWISH) return x * (1.0f / (1.0f + __expf(-x)));
+  if (ACT == ACT_LRELU) return x >= 0.f ? x : x * slope;
+  if (ACT == ACT_GELU) return gelu_fast(x);
   return x;
+}
+
+// One column quad through bias, activation and scale: act(a + bv) * sc, with
+// sc = alpha, or 0 in a masked row (the residual is added by the caller).
+template <int ACT>
+__device__ __forceinline__ float4 epi_quad(const float4 a, const float4 bv, float sc, float slope) {
+  if constexpr (ACT == ACT_GELU) {
+    const f2v g0 = gelu_fast2(f2v{a.x + bv.x, a.y + bv.y}) * sc, g1 = gelu_fast2(f2v{a.z + bv.z, a.w + bv.w}) * sc;
+    return make_float4(g0[0], g0[1], g1[0], g1[1]);
+  } else {
+    return make_float4(act_f<ACT>(a.x + bv.x, slope) * sc, act_f<ACT>(a.y + bv.y, slope) * sc,
+                       act_f<ACT>(a.z + bv.z, slope) * sc, act_f<ACT>(a.w + bv.w, slope) * sc);
+  }
 }
 
 struct G256 {
@@ -124,7 +135,7 @@ struct G256 {
   const uint8_t* SW;
   long long ldw, ldsw;        // bytes
   int M, N, K;                // K in elements
-  Gemm256Epi ep;
+  GemmEpi ep;
   int out_mode;               // 0 fp32, 1 bf16, 2 MXFP8 (MX only)
   uint8_t* out_scales;
   long long ldso;
@@ -413,15 +424,8 @@ __global__ void __launch_bounds__(NT, 1) gemm256_kernel(G256 p) {
         const int rl = (pg * 8 + q) * 4 + (lane >> 4);
         const int row = m0 + wm * 128 + hm * 64 + rl;
         const float4 a = *reinterpret_cast<const float4*>(cs + rl * CS_STRIDE + ocol);
-        const float sc = scv[q];
-        float v0, v1, v2, v3;
-        if constexpr (ACT == G_GELU) {
-          const f2v g0 = gelu_fast2(f2v{a.x + bv.x, a.y + bv.y}) * sc, g1 = gelu_fast2(f2v{a.z + bv.z, a.w + bv.w}) * sc;
-          v0 = g0[0]; v1 = g0[1]; v2 = g1[0]; v3 = g1[1];
-        } else {
-          v0 = act_f<ACT>(a.x + bv.x, p.ep.slope) * sc; v1 = act_f<ACT>(a.y + bv.y, p.ep.slope) * sc;
-          v2 = act_f<ACT>(a.z + bv.z, p.ep.slope) * sc; v3 = act_f<ACT>(a.w + bv.w, p.ep.slope) * sc;
-        }
+        const float4 v = epi_quad<ACT>(a, bv, scv[q], p.ep.slope);
+        float v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
         if (p.ep.res) {  // (no +0 when there is none: a -0 stays -0, as in the other kernels)
           v0 += rv[q].x;
           v1 += rv[q].y;
@@ -483,14 +487,8 @@ __global__ void __launch_bounds__(256) splitk_epi_kernel(G256 p) {
     const float4 x1 = *reinterpret_cast<const float4*>(p1 + rl * 256 + c);
     const float4 a = make_float4(x0.x + x1.x, x0.y + x1.y, x0.z + x1.z, x0.w + x1.w);
     const float sc = (p.ep.rowmask && p.ep.rowmask[row]) ? 0.f : p.ep.alpha;
-    float v0, v1, v2, v3;
-    if constexpr (ACT == G_GELU) {
-      const f2v g0 = gelu_fast2(f2v{a.x + bv.x, a.y + bv.y}) * sc, g1 = gelu_fast2(f2v{a.z + bv.z, a.w + bv.w}) * sc;
-      v0 = g0[0]; v1 = g0[1]; v2 = g1[0]; v3 = g1[1];
-    } else {
-      v0 = act_f<ACT>(a.x + bv.x, p.ep.slope) * sc; v1 = act_f<ACT>(a.y + bv.y, p.ep.slope) * sc;
-      v2 = act_f<ACT>(a.z + bv.z, p.ep.slope) * sc; v3 = act_f<ACT>(a.w + bv.w, p.ep.slope) * sc;
-    }
+    const float4 v = epi_quad<ACT>(a, bv, sc, p.ep.slope);
+    float v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
     if (p.ep.res) {
       const float4 r = *reinterpret_cast<const float4*>(p.ep.res + (long long)row * p.ep.ldr + gcol);
       v0 += r.x;
@@ -538,7 +536,7 @@ int launch_t(const G256& p, hipStream_t s, float* ws, long long ws_floats) {
   if constexpr (MX && OUT == 0) {
     const int tail = ws ? split_tail(p.M, p.N, p.K) : 0;
     if (tail && ws_floats >= 2LL * tail * 65536) {
-      if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&gemm256_kernel<true, G_NONE, 0>),
+      if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&gemm256_kernel<true, ACT_NONE, 0>),
                                         lds_bytes<true>()))
         return (int)e;
       G256 q = p;  // whole tiles: the first grid - tail of the launch order
@@ -550,11 +548,11 @@ int launch_t(const G256& p, hipStream_t s, float* ws, long long ws_floats) {
       h.ep.res = nullptr;
       h.ep.rowmask = nullptr;
       h.ep.alpha = 1.f;
-      h.ep.act = G_NONE;
+      h.ep.act = ACT_NONE;
       h.ksplit = 2;
       h.tile_base = grid - tail;
       h.part = ws;
-      hipLaunchKernelGGL((gemm256_kernel<true, G_NONE, 0>), dim3(2 * tail), dim3(NT), lds_bytes<true>(), s, h);
+      hipLaunchKernelGGL((gemm256_kernel<true, ACT_NONE, 0>), dim3(2 * tail), dim3(NT), lds_bytes<true>(), s, h);
       SBK_CHECK_LAUNCH();
       G256 f = p;  // the tail's epilogue
       f.tile_base = grid - tail;
@@ -574,18 +572,18 @@ int launch_t(const G256& p, hipStream_t s, float* ws, long long ws_floats) {
 template <bool MX, int OUT>
 int launch_o(const G256& p, hipStream_t s, float* ws = nullptr, long long ws_floats = 0) {
   switch (p.ep.act) {
-    case G_NONE: return launch_t<MX, G_NONE, OUT>(p, s, ws, ws_floats);
-    case G_SWISH:
+    case ACT_NONE: return launch_t<MX, ACT_NONE, OUT>(p, s, ws, ws_floats);
+    case ACT_SWISH:
       if constexpr (MX) return SBK_ERR_ARG;
-      else return launch_t<MX, G_SWISH, OUT>(p, s, ws, ws_floats);
-    case G_LRELU: return launch_t<MX, G_LRELU, OUT>(p, s, ws, ws_floats);
-    case G_GELU: return launch_t<MX, G_GELU, OUT>(p, s, ws, ws_floats);
+      else return launch_t<MX, ACT_SWISH, OUT>(p, s, ws, ws_floats);
+    case ACT_LRELU: return launch_t<MX, ACT_LRELU, OUT>(p, s, ws, ws_floats);
+    case ACT_GELU: return launch_t<MX, ACT_GELU, OUT>(p, s, ws, ws_floats);
     default: return SBK_ERR_ARG;
   }
 }
 
-bool epi_ok(const Gemm256Epi& ep) {
-  if (ep.act != G_NONE && ep.act != G_SWISH && ep.act != G_LRELU && ep.act != G_GELU) return false;
+bool epi_ok(const GemmEpi& ep) {
+  if (ep.act != ACT_NONE && ep.act != ACT_SWISH && ep.act != ACT_LRELU && ep.act != ACT_GELU) return false;
   const uintptr_t al = reinterpret_cast<uintptr_t>(ep.bias) | reinterpret_cast<uintptr_t>(ep.res) |
                        reinterpret_cast<uintptr_t>(ep.out);
   return !(al & 15) && !(ep.ldr & 3) && !(ep.ldc & 3);
@@ -594,14 +592,14 @@ bool epi_ok(const Gemm256Epi& ep) {
 }  // namespace
 
 bool gemm256_supported(int M, int N, int K, long long lda, long long ldw, const void* A, const void* W,
-                       const Gemm256Epi& ep) {
+                       const GemmEpi& ep) {
   if (M <= 0 || N <= 0 || K <= 0 || (N & 255) || (K & 63) || (lda & 7) || (ldw & 7)) return false;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return false;
   return epi_ok(ep);
 }
 
 int gemm256_launch(const void* A, long long lda, const void* W, long long ldw, int M, int N, int K,
-                   const Gemm256Epi& ep, hipStream_t s) {
+                   const GemmEpi& ep, hipStream_t s) {
   if (!gemm256_supported(M, N, K, lda, ldw, A, W, ep)) return SBK_ERR_ARG;
   G256 p{reinterpret_cast<const uint8_t*>(A), nullptr, lda * 2, 0, (long long)M, 0, 0,
          reinterpret_cast<const uint8_t*>(W), nullptr, ldw * 2, 0, M, N, K, ep, ep.out_bf16 ? 1 : 0, nullptr, 0};
@@ -610,13 +608,13 @@ int gemm256_launch(const void* A, long long lda, const void* W, long long ldw, i
 
 bool mx256_supported(int M, int N, int K, long long lda, long long ldsa, long long rpb, long long a_bs,
                      long long s_bs, long long ldw, long long ldsw, const void* A, const void* SA, const void* W,
-                     const void* SW, const Gemm256Epi& ep, int out_mode, const void* out_scales) {
+                     const void* SW, const GemmEpi& ep, int out_mode, const void* out_scales) {
   if (M <= 0 || N <= 0 || K <= 0 || (N & 255) || (K & 127) || rpb <= 0) return false;
   if ((lda | a_bs | ldw) & 15) return false;
   if ((ldsa | s_bs | ldsw) & 3) return false;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return false;
   if ((reinterpret_cast<uintptr_t>(SA) | reinterpret_cast<uintptr_t>(SW)) & 3) return false;
-  if (ep.act == G_SWISH || out_mode < 0 || out_mode > 2) return false;
+  if (ep.act == ACT_SWISH || out_mode < 0 || out_mode > 2) return false;
   if (out_mode == 2 && (!out_scales || (ep.ldc & 15) || (reinterpret_cast<uintptr_t>(ep.out) & 15))) return false;
   return epi_ok(ep);
 }
@@ -627,7 +625,7 @@ long long mx256_split_floats(int M, int N, int K, int out_mode) {
 
 int mx256_launch(const void* A, const void* SA, long long lda, long long ldsa, long long rpb, long long a_bs,
                  long long s_bs, const void* W, const void* SW, long long ldw, long long ldsw, int M, int N, int K,
-                 const Gemm256Epi& ep, int out_mode, void* out_scales, long long ldso, hipStream_t s, float* ws,
+                 const GemmEpi& ep, int out_mode, void* out_scales, long long ldso, hipStream_t s, float* ws,
                  long long ws_floats) {
   if (!mx256_supported(M, N, K, lda, ldsa, rpb, a_bs, s_bs, ldw, ldsw, A, SA, W, SW, ep, out_mode, out_scales))
     return SBK_ERR_ARG;
@@ -650,7 +648,7 @@ SBK_API int sbk_mx_gemm256(const uint8_t* A, const uint8_t* SA, long long lda, l
                            const float* res, long long ldr, void* out, long long ldc, int out_mode,
                            uint8_t* out_scales, long long ldso, void* stream) {
   if (ldr > 0x7fffffffLL || ldc > 0x7fffffffLL) return SBK_ERR_ARG;
-  const Gemm256Epi ep{bias, act, 0.f, res, (int)ldr, alpha, nullptr, out, (int)ldc, out_mode == 1};
+  const GemmEpi ep{bias, act, 0.f, res, (int)ldr, alpha, nullptr, out, (int)ldc, out_mode == 1};
   return mx256_launch(A, SA, lda, ldsa, rpb, a_bs, s_bs, W, SW, ldw, ldsw, M, N, K, ep, out_mode, out_scales, ldso,
                       (hipStream_t)stream);
 }

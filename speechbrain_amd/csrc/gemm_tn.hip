@@ -43,6 +43,16 @@ struct TnArgs {
   int M, N, K, kchunk, nsplit;
 };
 
+// blockIdx.z = batch * nsplit + split: advances the operands to this
+// workgroup's batch and gives its split's token range [k0, k1)
+template <typename T>
+__device__ __forceinline__ void tn_slice(const T*& A, const T*& B, float*& C, long long sA, long long sB, long long sC,
+                                         int K, int kchunk, int nsplit, int& k0, int& k1) {
+  const int bz = blockIdx.z / nsplit, sp = blockIdx.z - bz * nsplit;
+  k0 = sp * kchunk, k1 = min(K, k0 + kchunk);
+  A += bz * sA, B += bz * sB, C += bz * sC;
+}
+
 // BM x BN output tile (BM, BN in {64, 128}), 4 waves as 2 x 2, each wave
 // (BM / 2) x (BN / 2) = MI x NI MFMA tiles of 16 x 16.
 template <int BM, int BN>
@@ -52,18 +62,21 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(TnArgs a) {
   __shared__ __attribute__((aligned(16))) bf16_t Bs[TN_BK * TN_LD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int bz = blockIdx.z / a.nsplit, sp = blockIdx.z - bz * a.nsplit;
-  const int k0 = sp * a.kchunk, k1 = min(a.K, k0 + a.kchunk);
-  const bf16_t* A = a.A + bz * a.sA;
-  const bf16_t* B = a.B + bz * a.sB;
-  float* C = a.C + bz * a.sC;
+  const bf16_t *A = a.A, *B = a.B;
+  float* C = a.C;
+  int k0, k1;
+  tn_slice(A, B, C, a.sA, a.sB, a.sC, a.K, a.kchunk, a.nsplit, k0, k1);
   // chunk c of a step: row c / (BM / 8), columns 8 (c % (BM / 8)).  DEPTH
   // register sets: the loads of step kt + DEPTH are issued right after step
   // kt's set is stored to LDS.  Measured: DEPTH 4 (64-tile) / 2 (128-tile)
   // is no faster than 1 (the step is bound by its store -> barrier -> read
   // -> MFMA -> barrier chain, not by the global loads) and costs VGPRs.  A
   // double-buffered LDS variant (one barrier per step) was no faster either
-  // (t64: 117 vs 112 us at one split; profiles/r02_gemm_sweep*.log).
+  // (t64: 117 vs 112 us at one split; profiles/r02_gemm_sweep*.log).  The
+  // DEPTH loop nest stays although DEPTH is 1: written as one plain loop the
+  // 128-tile compiles to a different prologue and runs 4.6 % slower (181 ->
+  // 190 us at one split, the 64-tile 2 % faster;
+  // profiles/gemm_tile_primitives_timing.txt).
   constexpr int DEPTH = 1;
   uint4 ra[DEPTH][CA], rb[DEPTH][CB];
   auto gload = [&](uint4 (&xa)[CA], uint4 (&xb)[CB], int kb) __attribute__((always_inline)) {
@@ -163,11 +176,10 @@ __global__ void __launch_bounds__(256) gemm_tn_f32_kernel(const float* __restric
   __shared__ __attribute__((aligned(16))) float Bs[TF_BK * TF_LD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1;
   const int m0 = blockIdx.x * 64, n0 = blockIdx.y * 64;
-  const int bz = blockIdx.z / nsplit, sp = blockIdx.z - bz * nsplit;
-  const int k0 = sp * kchunk, k1 = min(K, k0 + kchunk);
-  const float* A = Ap + bz * sA;
-  const float* B = Bp + bz * sB;
-  float* C = Cp + bz * sC;
+  const float *A = Ap, *B = Bp;
+  float* C = Cp;
+  int k0, k1;
+  tn_slice(A, B, C, sA, sB, sC, K, kchunk, nsplit, k0, k1);
   // 32 k-rows x 64 columns = 512 float4 chunks per operand: 2 per thread
   float4 ra[2], rb[2];
   auto ld4 = [&](const float* X, long long ld, int r, int c, int lim) __attribute__((always_inline)) {
@@ -235,6 +247,25 @@ __global__ void __launch_bounds__(256) gemm_tn_f32_kernel(const float* __restric
     }
 }
 
+// The token-range split of a launch of tm x tn x batch workgroups per split:
+// nsplit <= 0 chooses — split until ~1024 workgroups, >= 256 rows each, and at most
+// ~4M fp32 atomics in all (L2 atomic throughput, not the MFMA loop, bounds a
+// many-way split: 32 splits of a 1024 x 256 dW ran at 88-168 TF/s).  Returns
+// the rows per split, a multiple of the kernel's K step bk, and sets nsplit to
+// the splits that many rows make.
+int tn_split(int M, int N, int K, int batch, int tm, int tn, int bk, int& nsplit) {
+  const long long tiles = (long long)tm * tn * batch;
+  if (nsplit <= 0) {
+    nsplit = 1;
+    while (tiles * nsplit * 2 <= 1024 && (long long)K / (nsplit * 2) >= 256 &&
+           (long long)M * N * batch * nsplit * 2 <= (4LL << 20))
+      nsplit *= 2;
+  }
+  const int kchunk = ((K + nsplit - 1) / nsplit + bk - 1) / bk * bk;
+  nsplit = (K + kchunk - 1) / kchunk;
+  return kchunk;
+}
+
 }  // namespace
 
 // C[b] += A[b]^T B[b] for b < batch.  A (K, M) with row stride lda, B (K, N)
@@ -257,25 +288,12 @@ SBK_API int sbk_gemm_tn_cfg(const void* A, long long lda, long long sA, const vo
   }
   if (tile != 64 && tile != 128) return SBK_ERR_ARG;
   const int tm = (M + tile - 1) / tile, tn = (N + tile - 1) / tile;
-  const long long tiles = (long long)tm * tn * batch;
-  if (nsplit <= 0) {
-    // split the token range until ~1024 workgroups, >= 256 rows each, and at
-    // most ~4M fp32 atomics in all (L2 atomic throughput, not the MFMA loop,
-    // bounds a many-way split: 32 splits of a 1024 x 256 dW ran at 88-168 TF/s)
-    nsplit = 1;
-    while (tiles * nsplit * 2 <= 1024 && (long long)K / (nsplit * 2) >= 256 &&
-           (long long)M * N * batch * nsplit * 2 <= (4LL << 20))
-      nsplit *= 2;
-  }
-  const int kchunk = ((K + nsplit - 1) / nsplit + TN_BK - 1) / TN_BK * TN_BK;
-  nsplit = (K + kchunk - 1) / kchunk;
+  const int kchunk = tn_split(M, N, K, batch, tm, tn, TN_BK, nsplit);
   if ((long long)batch * nsplit > 65535) return SBK_ERR_ARG;
   TnArgs a{reinterpret_cast<const bf16_t*>(A), reinterpret_cast<const bf16_t*>(B), C, lda, ldb, ldc, sA, sB, sC,
            M, N, K, kchunk, nsplit};
-  if (tile == 128)
-    hipLaunchKernelGGL((gemm_tn_kernel<128, 128>), dim3(tm, tn, batch * nsplit), dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((gemm_tn_kernel<64, 64>), dim3(tm, tn, batch * nsplit), dim3(256), 0, (hipStream_t)stream, a);
+  auto kern = tile == 128 ? gemm_tn_kernel<128, 128> : gemm_tn_kernel<64, 64>;
+  hipLaunchKernelGGL(kern, dim3(tm, tn, batch * nsplit), dim3(256), 0, (hipStream_t)stream, a);
   SBK_CHECK_LAUNCH();
   return 0;
 }
@@ -303,15 +321,7 @@ SBK_API int sbk_gemm_tn_f32(const float* A, long long lda, long long sA, const f
   const int vec = ((M | N) % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && (sA | sB) % 4 == 0 &&
                    ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0);
   const int tm = (M + 63) / 64, tn = (N + 63) / 64;
-  const long long tiles = (long long)tm * tn * batch;
-  if (nsplit == 0) {
-    nsplit = 1;
-    while (tiles * nsplit * 2 <= 1024 && (long long)K / (nsplit * 2) >= 256 &&
-           (long long)M * N * batch * nsplit * 2 <= (4LL << 20))
-      nsplit *= 2;
-  }
-  const int kchunk = ((K + nsplit - 1) / nsplit + TF_BK - 1) / TF_BK * TF_BK;
-  nsplit = (K + kchunk - 1) / kchunk;
+  const int kchunk = tn_split(M, N, K, batch, tm, tn, TF_BK, nsplit);
   if ((long long)batch * nsplit > 65535) return SBK_ERR_ARG;
   hipLaunchKernelGGL(gemm_tn_f32_kernel, dim3(tm, tn, batch * nsplit), dim3(256), 0, (hipStream_t)stream, A, B, C, lda,
                      ldb, ldc, sA, sB, sC, M, N, K, kchunk, nsplit, vec);

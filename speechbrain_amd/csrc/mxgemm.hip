@@ -55,7 +55,7 @@ struct MxArgs {
   long long ldw, ldsw;
   int M, N, K;
   const float* bias;
-  int act;                   // 0 none, 3 relu, 4 gelu
+  int act;                   // ACT_NONE, ACT_LRELU (slope 0: ReLU), ACT_GELU
   float alpha;
   const float* res;
   long long ldr;
@@ -88,8 +88,8 @@ __device__ __forceinline__ long long a_srow(const MxArgs& p, int m) {
 
 template <int ACT>
 __device__ __forceinline__ float act_f(float x) {
-  if (ACT == 4) return gelu_erf(x);
-  if (ACT == 3) return fmaxf(x, 0.f);
+  if (ACT == ACT_GELU) return gelu_erf(x);
+  if (ACT == ACT_LRELU) return fmaxf(x, 0.f);
   return x;
 }
 
@@ -486,21 +486,21 @@ static int mx_gemm_impl(const uint8_t* A, const uint8_t* SA, long long lda, long
   if (out_mode == 2 && (!out_scales || (ldc & 15) || (ldso & 3) ||
                         ((reinterpret_cast<uintptr_t>(out) & 15) | (reinterpret_cast<uintptr_t>(out_scales) & 3))))
     return SBK_ERR_ARG;
-  if (act != 0 && act != 3 && act != 4) return SBK_ERR_ARG;
+  if (act != ACT_NONE && act != ACT_LRELU && act != ACT_GELU) return SBK_ERR_ARG;
   MxArgs p{A, SA, lda, ldsa, rpb, a_bs, s_bs, W, SW, ldw, ldsw, M, N, K, bias, act, alpha, res, ldr,
            out, ldc, out_mode, out_scales, ldso};
   hipStream_t s = (hipStream_t)stream;
   // the 256 x 256 multi-phase kernel (gemm256.hip) when it fills the chip:
   // 1.1-1.5x these kernels on config 5's shapes (profiles/r05c_mx256.log)
   if (ldr <= 0x7fffffffLL && ldc <= 0x7fffffffLL && (long long)((M + 255) / 256) * (N / 256) >= 180) {
-    const Gemm256Epi ep{bias, act, 0.f, res, (int)ldr, alpha, nullptr, out, (int)ldc, out_mode == 1};
+    const GemmEpi ep{bias, act, 0.f, res, (int)ldr, alpha, nullptr, out, (int)ldc, out_mode == 1};
     if (mx256_supported(M, N, K, lda, ldsa, rpb, a_bs, s_bs, ldw, ldsw, A, SA, W, SW, ep, out_mode, out_scales))
       return mx256_launch(A, SA, lda, ldsa, rpb, a_bs, s_bs, W, SW, ldw, ldsw, M, N, K, ep, out_mode, out_scales, ldso,
                           s, ws, ws_floats);
   }
-  if (act == 4) return launch_act<4>(p, s);
-  if (act == 3) return launch_act<3>(p, s);
-  return launch_act<0>(p, s);
+  if (act == ACT_GELU) return launch_act<ACT_GELU>(p, s);
+  if (act == ACT_LRELU) return launch_act<ACT_LRELU>(p, s);
+  return launch_act<ACT_NONE>(p, s);
 }
 
 SBK_API int sbk_mx_gemm(const uint8_t* A, const uint8_t* SA, long long lda, long long ldsa, long long rpb,
