@@ -108,7 +108,9 @@ __device__ __forceinline__ f2v gelu_fast2(f2v x) {
 template <int ACT>
 __device__ __forceinline__ float act_f(float x, float slope) {
   if (ACT == ACT_SWISH) return x * (1.0f / (1.0f + __expf(-x)));
-  if (ACT == ACT_LRELU) return x >= 0.f ? x : x * slope;
+  // (+ 0.f: slope 0 — the MXFP8 entry points' ReLU — gives +0 for x < 0 as
+  // mxgemm.hip's fmaxf does, not the -0 of x * 0; the same bits otherwise)
+  if (ACT == ACT_LRELU) return x >= 0.f ? x : x * slope + 0.f;
   if (ACT == ACT_GELU) return gelu_fast(x);
   return x;
 }

@@ -487,6 +487,7 @@ static int mx_gemm_impl(const uint8_t* A, const uint8_t* SA, long long lda, long
                         ((reinterpret_cast<uintptr_t>(out) & 15) | (reinterpret_cast<uintptr_t>(out_scales) & 3))))
     return SBK_ERR_ARG;
   if (act != ACT_NONE && act != ACT_LRELU && act != ACT_GELU) return SBK_ERR_ARG;
+  if (out_mode < 0 || out_mode > 2) return SBK_ERR_ARG;  // (the launch switch's default is the MXFP8 store)
   MxArgs p{A, SA, lda, ldsa, rpb, a_bs, s_bs, W, SW, ldw, ldsw, M, N, K, bias, act, alpha, res, ldr,
            out, ldc, out_mode, out_scales, ldso};
   hipStream_t s = (hipStream_t)stream;
