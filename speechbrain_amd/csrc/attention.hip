@@ -25,6 +25,7 @@
 //    a stats pass then an exact pass that writes P and accumulates P·V.
 // bf16 operands use v_mfma_f32_16x16x32_bf16, fp32 operands exact f32 MFMA
 // (mfma.h); softmax and accumulators are fp32.
+#include "lds_dma.h"
 #include "mfma.h"
 
 using namespace sbk;
@@ -38,10 +39,7 @@ constexpr int PBR = KC + QB;  // positional band rows staged per chunk (127 used
 constexpr int GR = 80;        // G^T rows per wave (79 used)
 constexpr int GS = 20;        // G^T scratch row stride (floats): conflict-free writes and shifted reads
 
-template <typename T>
-struct VLayout {  // bf16: V row-major + ds_read_tr16 ; fp32: V^T staged transposed
-  static constexpr bool TR = sizeof(T) == 2;
-};
+constexpr float LOG2E = 1.4426950408889634f;
 
 template <typename T, int DHP>
 struct FlashLds {
@@ -49,10 +47,11 @@ struct FlashLds {
   // fragment reads and the ds_read_b64_tr_b16 V reads conflict-free (+16 B
   // left 2-way conflicts); fp32: +16 B
   static constexpr int PAD = sizeof(T) == 2 ? 2 * MT<T>::PAD : MT<T>::PAD;
+  static constexpr bool TRV = sizeof(T) == 2;  // bf16: V row-major + ds_read_tr16; fp32: V^T staged transposed
   static constexpr int KR = DHP + PAD;  // Ks / Ps / V(row-major) row stride
   static constexpr int VR = KC + PAD;   // Vt row stride (fp32 path)
   static constexpr size_t ks = (size_t)KC * KR * sizeof(T);
-  static constexpr size_t vt = VLayout<T>::TR ? (size_t)KC * KR * sizeof(T) : (size_t)DHP * VR * sizeof(T);
+  static constexpr size_t vt = TRV ? (size_t)KC * KR * sizeof(T) : (size_t)DHP * VR * sizeof(T);
   static constexpr size_t ps = (size_t)PBR * KR * sizeof(T);
   static constexpr size_t gs = (size_t)4 * GR * GS * 4;
   static constexpr size_t ms = (size_t)(KC + 4) * 4;  // key mask + 'chunk has a masked key' flag
@@ -64,32 +63,86 @@ struct FlashLds {
   static constexpr size_t bytes = ks + ps + vt + ms;
 };
 
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
 // Out-of-range K / V / positional rows are zeroed at commit.  (Tried:
 // committing the clamped loads unmasked — the rows only meet masked scores —
 // measured 36 -> 54 us: the compiler then sank the prefetch loads to their
 // stores; and head dims >= dh must stay zero when dh is not a multiple of the
 // 8-dim Q fragment, whose vector loads then read the next section.)
-#define STAGE_SEL(ok, v) sel4((ok), (v))
-
 // component-wise select (a struct-valued ?: takes the operands' addresses and
 // sends the staging arrays to scratch)
 __device__ __forceinline__ uint4 sel4(bool c, const uint4& a) {
   return make_uint4(c ? a.x : 0u, c ? a.y : 0u, c ? a.z : 0u, c ? a.w : 0u);
 }
 
-// A-operand fragment of V^T (rows d = dbase + (lane&15)) for keys
-// {k0 + 4g .. k0 + 4g + 3} ∪ {k0 + 16 + 4g .. +3}, read from row-major V in
-// LDS with two transposing reads (ds_read_b64_tr_b16): lane 4q+p of each
-// 16-lane group addresses row (key) q, columns (d) 4p..4p+3 of the block.
-__device__ __forceinline__ bf16x8 vt_frag_tr(const bf16_t* V, int KR, int k0, int dbase, int lane) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const bf16_t* a0 = V + (k0 + 4 * g + q) * KR + dbase + 4 * p;
-  const bf16_t* a1 = a0 + 16 * KR;
-  const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a0));
-  const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a1));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+// ---------------------------------------------------------------------------
+// Pieces shared by the two kernels below (the k-transposed V fragment reader
+// is frag_tr of mfma.h, the LDS-DMA piece lds_dma16 of lds_dma.h).  Each kernel
+// keeps its own Q-fragment build, S^T / G^T and P·V loops and output store:
+// written as shared steps they changed the LDS-DMA kernel's chunk loop or
+// added spills to the general kernel
+// (profiles/attn_tile_primitives_asm_vs_parent.md).  The row max / row sum
+// reductions differ on purpose: they round differently.
+// ---------------------------------------------------------------------------
+
+// Where a workgroup works: head h of utterance b, queries i0 .. i0 + QB - 1.
+// XCD-aware bijective remap: workgroups are dealt round-robin to the 8 XCDs;
+// give each XCD a contiguous run of tiles so the query blocks of one (b, h)
+// share an L2 and its K/V/positional rows are fetched from HBM once.
+template <typename T>
+struct TileOrigin {
+  int tile, h, b, i0, d_model;
+  long long row3;  // qkv row stride
+  const T* qkv_b;  // this (b, h)'s [q|k|v] section of row 0
+  const T* pk_h;   // this head's columns of the positional rows
+};
+template <typename T>
+__device__ __forceinline__ TileOrigin<T> tile_origin(const T* qkv, const T* pk, int Tn, int H, int dh) {
+  TileOrigin<T> o;
+  o.d_model = H * dh;
+  o.row3 = 3LL * o.d_model;
+  const int nqb = (Tn + QB - 1) / QB;
+  o.tile = xcd_tile(gridDim.x, blockIdx.x);
+  const int qb = o.tile % nqb, bh = o.tile / nqb;
+  o.h = bh % H;
+  o.b = bh / H;
+  o.i0 = qb * QB;
+  o.qkv_b = qkv + (long long)o.b * Tn * o.row3 + o.h * 3 * dh;
+  o.pk_h = pk + o.h * dh;
+  return o;
+}
+
+// ---- key mask staging and softmax step of the general kernel ----
+// additive key mask of key j: -inf past Tn and for a padded key
+__device__ __forceinline__ float key_mask(const uint8_t* kpm, int b, int j, int Tn) {
+  return (j < Tn && !(kpm && kpm[(long long)b * Tn + min(j, Tn - 1)])) ? 0.f : -INFINITY;
+}
+// wave 0 (KC == 64): mask values and the chunk's any-masked flag
+__device__ __forceinline__ void stage_mask(float* Ms, int tid, float mv) {
+  Ms[tid] = mv;
+  const bool anym = __any(mv != 0.f);
+  if (tid == 0) reinterpret_cast<int*>(Ms)[KC] = anym;
+}
+// One chunk of the online softmax: p = exp2(sc - max), row sum as a serial
+// sum and two xor-shuffles, l_run / m_run updated; returns the rescale of
+// what was accumulated under the old maximum.
+__device__ __forceinline__ float chunk_expsum(const float (&sc)[4][4], float cmax, float& m_run, float& l_run,
+                                              float (&p)[4][4]) {
+  const float m_new = fmaxf(m_run, cmax);
+  const float mref = m_new == -INFINITY ? 0.f : m_new;
+  const float alpha = __builtin_amdgcn_exp2f(m_run - mref);
+  float ls = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[t][r] = __builtin_amdgcn_exp2f(sc[t][r] - mref);
+      ls += p[t][r];
+    }
+  ls += __shfl_xor(ls, 16);
+  ls += __shfl_xor(ls, 32);
+  l_run = l_run * alpha + ls;
+  m_run = m_new;
+  return alpha;
 }
 
 // s_memtime marks of the waves of one workgroup, and per workgroup its
@@ -102,7 +155,7 @@ template <typename T, int DHP, bool PROBS>
 __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restrict__ qkv, const T* __restrict__ pk,
                                                            const float* __restrict__ pbu,
                                                            const float* __restrict__ pbv,
-                                                           const uint8_t* __restrict__ kpm, int B, int Tn, int H,
+                                                           const uint8_t* __restrict__ kpm, int Tn, int H,
                                                            int dh, float scale, T* __restrict__ out,
                                                            float* __restrict__ probs, int vec_ok, int ldp,
                                                            const float* __restrict__ am, long long am_sb,
@@ -110,7 +163,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
   using Tr = MT<T>;
   using L = FlashLds<T, DHP>;
   constexpr int KR = L::KR, VR = L::VR, VEC = Tr::VEC;
-  constexpr bool TRV = VLayout<T>::TR;
+  constexpr bool TRV = L::TRV;
   constexpr int KS = DHP / 32;   // k-steps over the head dim
   constexpr int NDT = DHP / 16;  // O^T tiles (head-dim rows)
   constexpr int CPR = DHP / VEC; // 16-B chunks per staged row
@@ -123,31 +176,21 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
   T* Vs = reinterpret_cast<T*>(smem + L::ks + L::ps);
   float* Gs = reinterpret_cast<float*>(smem);  // over Ks + Ps (dead after the S / G MFMAs)
   float* Ms = reinterpret_cast<float*>(smem + L::ks + L::ps + L::vt);
-  constexpr bool ALIAS = true;
 
-  const int d_model = H * dh;
-  const long long row3 = 3LL * d_model;
-  const int nqb = (Tn + QB - 1) / QB;
-  // XCD-aware bijective remap: workgroups are dealt round-robin to the 8 XCDs;
-  // give each XCD a contiguous run of tiles so the query blocks of one (b, h)
-  // share an L2 and its K/V/positional rows are fetched from HBM once.
-  const int tile = xcd_tile(gridDim.x, blockIdx.x);
-  const int qb = tile % nqb;
-  const int bh = tile / nqb;
-  const int h = bh % H, b = bh / H;
-  const int i0 = qb * QB;
-  SBK_PROBE(const bool tl_on = tile == 200 && sizeof(T) == 2 && !PROBS;)
+  const TileOrigin<T> o = tile_origin(qkv, pk, Tn, H, dh);
+  const int h = o.h, b = o.b, i0 = o.i0;
+  const long long row3 = o.row3;
+  const T* qkv_b = o.qkv_b;
+  const T* pk_h = o.pk_h;
+  SBK_PROBE(const bool tl_on = o.tile == 200 && sizeof(T) == 2 && !PROBS;)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c16 = lane & 15, g = lane >> 4;
-  const int i0w = i0 + 16 * w;
-  const int my_i = i0w + c16;  // this lane's query
-  const T* qkv_b = qkv + (long long)b * Tn * row3 + h * 3 * dh;
-  const T* pk_h = pk + h * dh;
+  const int my_i = i0 + 16 * w + c16;  // this lane's query
   float* Gw = Gs + w * GR * GS;
 
   // ---- Qu / Qv as B-operand fragments (query on the lane), pre-scaled by
   // scale * log2(e) so scores come out of the MFMAs in the exp2 domain ----
-  const float qscale = scale * 1.4426950408889634f;
+  const float qscale = scale * LOG2E;
   typename Tr::frag fqu[KS], fqv[KS];
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
@@ -228,18 +271,15 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
       rp[i] = *reinterpret_cast<const uint4*>(pk_h + (long long)min(max(r, 0), 2 * Tn - 2) * ldp +
                                               min(d, dh - VEC));
     }
-    if (tid < KC) {
-      const int j = j0 + tid;
-      rm = (j < Tn && !(kpm && kpm[(long long)b * Tn + min(j, Tn - 1)])) ? 0.f : -INFINITY;
-    }
+    if (tid < KC) rm = key_mask(kpm, b, j0 + tid, Tn);
   };
   auto commit = [&](bool need_v) {
 #pragma unroll
     for (int i = 0; i < NKC; ++i) {
       const int c = tid + 256 * i, r = c / CPR, d = (c % CPR) * VEC;
-      *reinterpret_cast<uint4*>(Ks + r * KR + d) = STAGE_SEL(okk[i], rk[i]);
+      *reinterpret_cast<uint4*>(Ks + r * KR + d) = sel4(okk[i], rk[i]);
       if (need_v) {
-        const uint4 vv = STAGE_SEL(okk[i], rv[i]);
+        const uint4 vv = sel4(okk[i], rv[i]);
         if (TRV) {
           *reinterpret_cast<uint4*>(Vs + r * KR + d) = vv;
         } else {
@@ -252,13 +292,9 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
 #pragma unroll
     for (int i = 0; i < NPC; ++i) {
       const int c = tid + 256 * i, rr = c / CPR, d = (c % CPR) * VEC;
-      *reinterpret_cast<uint4*>(Ps + rr * KR + d) = STAGE_SEL(okp[i], rp[i]);
+      *reinterpret_cast<uint4*>(Ps + rr * KR + d) = sel4(okp[i], rp[i]);
     }
-    if (tid < KC) {  // wave 0 (KC == 64): mask values and the chunk's any-masked flag
-      Ms[tid] = rm;
-      const bool anym = __any(rm != 0.f);
-      if (tid == 0) reinterpret_cast<int*>(Ms)[KC] = anym;
-    }
+    if (tid < KC) stage_mask(Ms, tid, rm);
   };
   auto stage_scalar = [&](int j0, bool need_v) {  // unaligned head dims (e.g. d=144, H=4)
     const int rbase = Tn - QB - i0 + j0;
@@ -279,13 +315,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
       Ps[rr * KR + d] = (rr < PBR - 1 && r >= 0 && r <= 2 * Tn - 2 && d < dh) ? pk_h[(long long)r * ldp + d]
                                                                               : Tr::from_f32(0.f);
     }
-    if (tid < KC) {
-      const int j = j0 + tid;
-      const float mv = (j < Tn && !(kpm && kpm[(long long)b * Tn + j])) ? 0.f : -INFINITY;
-      Ms[tid] = mv;
-      const bool anym = __any(mv != 0.f);
-      if (tid == 0) reinterpret_cast<int*>(Ms)[KC] = anym;
-    }
+    if (tid < KC) stage_mask(Ms, tid, key_mask(kpm, b, j0 + tid, Tn));
   };
 
   constexpr int NPASS = PROBS ? 2 : 1;
@@ -329,7 +359,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
 #pragma unroll
         for (int t = 0; t < 5; ++t) Tr::mma(acc_g[t], fpb[t], fqv[s]);
       }
-      if (ALIAS) __syncthreads();  // every wave's Ks / Ps fragment reads are done: the scratch may overwrite them
+      __syncthreads();  // every wave's Ks / Ps fragment reads are done: the scratch may overwrite them
 #pragma unroll
       for (int t = 0; t < 5; ++t)
 #pragma unroll
@@ -354,27 +384,17 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
           const int jj = 16 * t + 4 * g + r;
           float v = acc_s[t][r] + Gw[(15 - c16 + jj) * GS + c16];
           if (masked_chunk) v += Ms[jj];
-          if (amrow && j0 + jj < Tn) v += amrow[j0 + jj] * 1.4426950408889634f;
+          if (amrow && j0 + jj < Tn) v += amrow[j0 + jj] * LOG2E;
           sc[t][r] = v;
           cmax = fmaxf(cmax, v);
         }
       cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
       cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
 
+      float p[4][4];
       if (stats_only) {
-        const float m_new = fmaxf(m_run, cmax);
-        const float mref = m_new == -INFINITY ? 0.f : m_new;
-        float ls = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ls += __builtin_amdgcn_exp2f(sc[t][r] - mref);
-        ls += __shfl_xor(ls, 16);
-        ls += __shfl_xor(ls, 32);
-        l_run = l_run * __builtin_amdgcn_exp2f(m_run - mref) + ls;
-        m_run = m_new;
+        chunk_expsum(sc, cmax, m_run, l_run, p);
       } else {
-        float p[4][4];
         if (PROBS) {
           const float mref = m_run == -INFINITY ? 0.f : m_run;
           const float inv = 1.0f / l_run;
@@ -388,21 +408,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
               if (my_i < Tn && j < Tn) prow[j] = p[t][r];
             }
         } else {
-          const float m_new = fmaxf(m_run, cmax);
-          const float mref = m_new == -INFINITY ? 0.f : m_new;
-          const float alpha = __builtin_amdgcn_exp2f(m_run - mref);
-          float ls = 0.f;
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              p[t][r] = __builtin_amdgcn_exp2f(sc[t][r] - mref);
-              ls += p[t][r];
-            }
-          ls += __shfl_xor(ls, 16);
-          ls += __shfl_xor(ls, 32);
-          l_run = l_run * alpha + ls;
-          m_run = m_new;
+          const float alpha = chunk_expsum(sc, cmax, m_run, l_run, p);
 #pragma unroll
           for (int t = 0; t < NDT; ++t) acc_o[t] *= alpha;
         }
@@ -421,7 +427,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
           for (int t = 0; t < NDT; ++t) {
             typename Tr::frag fa;
             if constexpr (TRV) {
-              fa = vt_frag_tr(reinterpret_cast<const bf16_t*>(Vs), KR, 32 * s2, 16 * t, lane);
+              fa = frag_tr(Vs, KR, 32 * s2, 16 * t, lane);
             } else {
               const T* vrow = Vs + (16 * t + c16) * VR + 32 * s2 + 4 * g;
               fa = Tr::load2x4(vrow, vrow + 16);
@@ -446,7 +452,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
   // ---- write O (row = this lane's query, cols d = 16t + 4g + r) ----
   if (my_i < Tn) {
     const float inv = PROBS ? 1.0f : 1.0f / l_run;
-    T* orow = out + ((long long)b * Tn + my_i) * d_model + h * dh;
+    T* orow = out + ((long long)b * Tn + my_i) * o.d_model + h * dh;
 #pragma unroll
     for (int t = 0; t < NDT; ++t) {
       const int d = 16 * t + 4 * g;
@@ -472,7 +478,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
 // ---------------------------------------------------------------------------
 // The encoder's inference path — bf16, dh = 64, no probabilities — with
 // three workgroups per CU.  The kernel above carries the next chunk's K / V /
-// band rows in 32 VGPRs (194 in all), so it runs two waves per SIMD: at
+// band rows in 32 VGPRs (212 in all), so it runs two waves per SIMD: at
 // B = 32, T = 376 its 768 workgroups take 1.5 rounds of 512.  Its score
 // assembly was also 16 serialised LDS round trips per chunk (a per-chunk
 // "any key masked" branch split it into read -> wait -> add steps).
@@ -504,7 +510,7 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
 // The tiles are distinct __shared__ objects and the other LDS accesses come
 // before a DMA is issued, so the compiler's LDS-DMA alias guard (a vmcnt wait
 // before an LDS access it cannot tell apart from a DMA in flight) has little
-// to wait for.  50 KB of LDS and <= 168 VGPRs: three workgroups per CU.
+// to wait for.  50 KB of LDS and 144 VGPRs (76 without the band): three workgroups per CU.
 namespace dmak {
 typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int RB = 64;   // bf16 per staged row (dh = 64): 128 B
@@ -512,17 +518,14 @@ constexpr int PB = 128;  // band rows staged per chunk (127 used)
 constexpr int G2 = 72;   // G scratch row (floats): 18 16-B slots, ≡ 2 mod 4
 constexpr int GO = 4;    // scratch index of key 0 (spare slots GO - 1 and GO + KC)
 __device__ __forceinline__ int swz_kp(int row) { return (row >> 1) & 7; }
+// V's chunk swizzle; equal for rows r and r + 16 (frag_tr)
 __device__ __forceinline__ int swz_v(int row) { return ((row >> 1) & 3) << 1; }
-// One LDS-DMA piece (64 lanes x 16 B to lds + 16 * lane), issued from inline
-// asm: the compiler then sees no LDS write in flight and puts no alias-guard
-// vmcnt wait before the LDS reads of the other tiles (with the builtin it
-// waited for the next chunk's K / band before the P·V reads).  dma_barrier's
-// vmcnt(0) + s_barrier is what orders the fills and the reads.
-__device__ __forceinline__ void dma16(const bf16_t* src, bf16_t* lds) {
-  const uint32_t la = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(uintptr_t)((__attribute__((address_space(3))) bf16_t*)lds));
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(la) : "memory", "m0");
-}
+// One LDS-DMA piece (lds_dma16: 64 lanes x 16 B to lds + 16 * lane; with the
+// builtin the compiler waited for the next chunk's K / band before the P·V
+// reads).  dma_barrier's vmcnt(0) + s_barrier is what orders the fills and
+// the reads.
+__device__ __forceinline__ void dma16(const bf16_t* src, bf16_t* lds) { lds_dma16(src, lds_addr(lds)); }
+
 // The same piece from a wave-uniform base (SGPR pair) plus a per-lane byte
 // offset computed once before the chunk loop; m0 (the LDS destination) is a
 // precomputed scalar.  The interior chunks issue their DMAs with no VALU
@@ -532,25 +535,11 @@ __device__ __forceinline__ void dma16(const bf16_t* src, bf16_t* lds) {
 __device__ __forceinline__ void dma16s(const void* sbase, uint32_t voff, uint32_t la) {
   asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(la) : "memory", "m0");
 }
-__device__ __forceinline__ uint32_t lds_addr(const void* lds) {
-  return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)lds));
-}
 // this wave's DMA pieces and LDS accesses done, then the workgroup barrier
 __device__ __forceinline__ void dma_barrier() {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-}
-// V^T A-operand fragment (as vt_frag_tr) from the swizzled V tile;
-// swz_v(r + 16) == swz_v(r)
-__device__ __forceinline__ bf16x8 vt_frag_swz(const bf16_t* V, int k0, int dbase, int lane) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int r0 = k0 + 4 * g + q, col = dbase + 4 * p;
-  const bf16_t* a0 = V + r0 * RB + ((((col >> 3) ^ swz_v(r0)) << 3) | (col & 7));
-  const bf16_t* a1 = a0 + 16 * RB;
-  const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a0));
-  const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a1));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 }  // namespace dmak
 
@@ -573,19 +562,15 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
   __shared__ __attribute__((aligned(16))) float Gs[BAND ? 4 * 16 * G2 : 4];
   __shared__ unsigned long long Mb[4];  // per-wave partial bitmaps of the chunks holding a padded key
 
-  const int d_model = H * dh;
-  const long long row3 = 3LL * d_model;
-  const int nqb = (Tn + QB - 1) / QB;
-  const int orig = blockIdx.x, tile = xcd_tile(gridDim.x, orig);  // XCD-aware bijective remap, as above
-  const int qb = tile % nqb, bh = tile / nqb;
-  const int h = bh % H, b = bh / H;
-  const int i0 = qb * QB;
+  const TileOrigin<bf16_t> o = tile_origin(qkv, pk, Tn, H, dh);
+  const int h = o.h, b = o.b, i0 = o.i0;
+  const long long row3 = o.row3;
+  const bf16_t* qkv_b = o.qkv_b;
+  const bf16_t* pk_h = o.pk_h;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c16 = lane & 15, g = lane >> 4;
   const int my_i = i0 + 16 * w + c16;
-  SBK_PROBE(const bool tl_on = tile == 200;)
-  const bf16_t* qkv_b = qkv + (long long)b * Tn * row3 + h * 3 * dh;
-  const bf16_t* pk_h = pk + h * dh;
+  SBK_PROBE(const int orig = blockIdx.x; const bool tl_on = o.tile == 200;)
   float* gq = Gs + w * 16 * G2 + c16 * G2 + GO;  // this lane's query row of the G scratch, at key 0
   const int lrow = lane >> 3, lchk = lane & 7;   // DMA piece: 8 rows x 8 16-B chunks
 
@@ -674,7 +659,7 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
   uint32_t mlo = 0, mhi = 0;  // the merged bitmap (wave-uniform)
 
   // Qu / Qv B-operand fragments, pre-scaled into the exp2 domain
-  const float qscale = scale * 1.4426950408889634f;
+  const float qscale = scale * LOG2E;
   bf16x8 fqu[2], fqv[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -824,7 +809,6 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc_o[t] *= alpha;
     ATT_TL(4 + 5 * ch);
-    // O^T += V^T · P^T (2 k-steps of 32 keys, permuted-k fragments as above)
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       float pv[8];
@@ -836,13 +820,13 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
       const bf16x8 fp = MT<bf16_t>::from8(pv);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        acc_o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt_frag_swz(Vs, 32 * s2, 16 * t, lane), fp, acc_o[t], 0, 0, 0);
+        acc_o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr(Vs, RB, 32 * s2, 16 * t, lane, swz_v), fp, acc_o[t], 0, 0, 0);
     }
     ATT_TL(5 + 5 * ch);
   }
   if (my_i < Tn) {
     const float inv = 1.0f / l_run;
-    bf16_t* orow = out + ((long long)b * Tn + my_i) * d_model + h * dh;
+    bf16_t* orow = out + ((long long)b * Tn + my_i) * o.d_model + h * dh;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       uint2 pk2;
@@ -858,41 +842,52 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
   })
 }
 
+bool aligned16(const void* a, const void* b, const void* c) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) % 16) == 0;
+}
+
 int launch_dma(const void* qkv, const void* pk, int ldp, const float* pbu, const float* pbv, const uint8_t* kpm, int B,
                int Tn, int H, float scale, void* out, hipStream_t s) {
   const int grid = B * H * ((Tn + QB - 1) / QB);
-  if (pk)
-    hipLaunchKernelGGL(relpos_flash_dma_kernel<true>, dim3(grid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(qkv),
-                       reinterpret_cast<const bf16_t*>(pk), ldp, pbu, pbv, kpm, Tn, H, scale,
-                       reinterpret_cast<bf16_t*>(out));
-  else
-    hipLaunchKernelGGL(relpos_flash_dma_kernel<false>, dim3(grid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(qkv),
-                       nullptr, 0, nullptr, nullptr, kpm, Tn, H, scale, reinterpret_cast<bf16_t*>(out));
+  const auto kern = pk ? relpos_flash_dma_kernel<true> : relpos_flash_dma_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(qkv),
+                     reinterpret_cast<const bf16_t*>(pk), ldp, pbu, pbv, kpm, Tn, H, scale,
+                     reinterpret_cast<bf16_t*>(out));
   SBK_CHECK_LAUNCH();
   return 0;
 }
 
-template <typename T, int DHP>
-int launch(const void* qkv, const void* pk, int ldp, const float* pbu, const float* pbv, const uint8_t* kpm, int B,
-           int Tn, int H, int dh, float scale, void* out, float* probs, hipStream_t s, const float* am = nullptr,
-           long long am_sb = 0, long long am_sh = 0) {
-  constexpr size_t lds = FlashLds<T, DHP>::bytes;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  const int grid = B * H * ((Tn + QB - 1) / QB);
-  const int VEC = MT<T>::VEC;
-  const int d_model = H * dh;
-  const int vec_ok = (dh % VEC == 0) && (d_model % VEC == 0) && (ldp % VEC == 0) &&
-                     ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(pk) | reinterpret_cast<uintptr_t>(out)) % 16 == 0);
-  if (probs)
-    hipLaunchKernelGGL((relpos_flash_kernel<T, DHP, true>), dim3(grid), dim3(256), lds, s,
-                       reinterpret_cast<const T*>(qkv), reinterpret_cast<const T*>(pk), pbu, pbv, kpm, B, Tn, H, dh,
-                       scale, reinterpret_cast<T*>(out), probs, vec_ok, ldp, am, am_sb, am_sh);
-  else
-    hipLaunchKernelGGL((relpos_flash_kernel<T, DHP, false>), dim3(grid), dim3(256), lds, s,
-                       reinterpret_cast<const T*>(qkv), reinterpret_cast<const T*>(pk), pbu, pbv, kpm, B, Tn, H, dh,
-                       scale, reinterpret_cast<T*>(out), probs, vec_ok, ldp, am, am_sb, am_sh);
-  SBK_CHECK_LAUNCH();
-  return 0;
+// The general kernel's instantiation for a dtype and head dim: f gets an
+// Inst<T, DHP> tag.
+template <typename T_, int DHP_>
+struct Inst {
+  using T = T_;
+  static constexpr int DHP = DHP_;
+};
+template <typename F>
+auto with_inst(int dtype_bf16, int dh, F f) {
+  if (dtype_bf16) return dh <= 64 ? f(Inst<bf16_t, 64>{}) : f(Inst<bf16_t, 128>{});
+  return dh <= 64 ? f(Inst<float, 64>{}) : f(Inst<float, 128>{});
+}
+
+int launch(int dtype_bf16, const void* qkv, const void* pk, int ldp, const float* pbu, const float* pbv,
+           const uint8_t* kpm, int B, int Tn, int H, int dh, float scale, void* out, float* probs, hipStream_t s,
+           const float* am = nullptr, long long am_sb = 0, long long am_sh = 0) {
+  return with_inst(dtype_bf16, dh, [&](auto inst) {
+    using T = typename decltype(inst)::T;
+    constexpr int DHP = decltype(inst)::DHP;
+    constexpr size_t lds = FlashLds<T, DHP>::bytes;
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    const int grid = B * H * ((Tn + QB - 1) / QB);
+    const int VEC = MT<T>::VEC;
+    const int vec_ok = (dh % VEC == 0) && ((H * dh) % VEC == 0) && (ldp % VEC == 0) && aligned16(qkv, pk, out);
+    const auto kern = probs ? relpos_flash_kernel<T, DHP, true> : relpos_flash_kernel<T, DHP, false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, reinterpret_cast<const T*>(qkv),
+                       reinterpret_cast<const T*>(pk), pbu, pbv, kpm, Tn, H, dh, scale, reinterpret_cast<T*>(out), probs,
+                       vec_ok, ldp, am, am_sb, am_sh);
+    SBK_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 }  // namespace
@@ -906,14 +901,9 @@ SBK_API int sbk_relpos_attention_ld(int dtype_bf16, const void* qkv, const void*
   if (B <= 0 || Tn <= 0 || H <= 0 || dh <= 0 || dh > 128 || ldp < H * dh || !pk) return SBK_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   // the encoder's inference path: bf16, dh = 64, no probabilities
-  if (dtype_bf16 && dh == 64 && !probs && ldp % 8 == 0 && Tn <= 64 * 64 &&
-      ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(pk) | reinterpret_cast<uintptr_t>(out)) % 16) == 0)
+  if (dtype_bf16 && dh == 64 && !probs && ldp % 8 == 0 && Tn <= 64 * 64 && aligned16(qkv, pk, out))
     return launch_dma(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, scale, out, s);
-  if (dtype_bf16)
-    return dh <= 64 ? launch<bf16_t, 64>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s)
-                    : launch<bf16_t, 128>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s);
-  return dh <= 64 ? launch<float, 64>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s)
-                  : launch<float, 128>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s);
+  return launch(dtype_bf16, qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s);
 }
 
 // Plain scaled dot-product attention over the same head-interleaved qkv
@@ -922,9 +912,7 @@ SBK_API int sbk_relpos_attention_ld(int dtype_bf16, const void* qkv, const void*
 // takes sbk_relpos_attention_ld with a zero band).
 SBK_API int sbk_mha_attention(const void* qkv, const uint8_t* kpm, int B, int Tn, int H, int dh, float scale, void* out,
                               void* stream) {
-  if (B <= 0 || Tn <= 0 || H <= 0 || dh != 64 || Tn > 64 * 64 ||
-      ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) % 16) != 0)
-    return SBK_ERR_ARG;
+  if (B <= 0 || Tn <= 0 || H <= 0 || dh != 64 || Tn > 64 * 64 || !aligned16(qkv, nullptr, out)) return SBK_ERR_ARG;
   return launch_dma(qkv, nullptr, 0, nullptr, nullptr, kpm, B, Tn, H, scale, out, (hipStream_t)stream);
 }
 
@@ -946,16 +934,8 @@ SBK_API int sbk_relpos_attention_mask(int dtype_bf16, const void* qkv, const voi
   if (B <= 0 || Tn <= 0 || H <= 0 || dh <= 0 || dh > 128 || ldp < H * dh || !pk || !am || am_sb < 0 ||
       am_sh < 0)
     return SBK_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype_bf16)
-    return dh <= 64 ? launch<bf16_t, 64>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s, am, am_sb,
-                                         am_sh)
-                    : launch<bf16_t, 128>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s, am, am_sb,
-                                          am_sh);
-  return dh <= 64 ? launch<float, 64>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s, am, am_sb,
-                                      am_sh)
-                  : launch<float, 128>(qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, s, am, am_sb,
-                                       am_sh);
+  return launch(dtype_bf16, qkv, pk, ldp, pbu, pbv, kpm, B, Tn, H, dh, scale, out, probs, (hipStream_t)stream, am, am_sb,
+                am_sh);
 }
 
 SBK_PROBE_EXPORT(sbk_probe_att_tl, g_att_tl)
@@ -963,6 +943,7 @@ SBK_PROBE_EXPORT(sbk_probe_att_wg, g_att_wg)
 
 SBK_API long long sbk_relpos_attention_lds(int dtype_bf16, int Tn, int dh) {
   (void)Tn;
-  if (dtype_bf16) return dh <= 64 ? (long long)FlashLds<bf16_t, 64>::bytes : (long long)FlashLds<bf16_t, 128>::bytes;
-  return dh <= 64 ? (long long)FlashLds<float, 64>::bytes : (long long)FlashLds<float, 128>::bytes;
+  return with_inst(dtype_bf16, dh, [](auto inst) {
+    return (long long)FlashLds<typename decltype(inst)::T, decltype(inst)::DHP>::bytes;
+  });
 }

@@ -49,6 +49,7 @@
 // prologue of the layer-chain kernel (convstage.h, 8 waves, an image-fed
 // 2-slot weight ring); this kernel serves the last layer and every caller of
 // sbk_conv_module / sbk_conv_module_pre.
+#include "lds_dma.h"
 #include "mfma.h"
 
 using namespace sbk;
@@ -125,17 +126,6 @@ __device__ __forceinline__ bf16x8 ld8g(const bf16_t* p) { return *reinterpret_ca
 // then cover all 64 banks.  (The former (row >> 2) & 3 assumed 16 contiguous
 // lanes: 2-way conflicts on every fragment read, 96 of the 226 conflict
 // cycles per wave that SQ_LDS_BANK_CONFLICT counted.)
-// (m0 is a reserved register: the clobber is advisory.  This kernel has no
-// other m0 user — every m0 write in its ISA is this one — so nothing the
-// compiler keeps in m0 can be overwritten.)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void cm_dma(const bf16_t* src, bf16_t* lds) {
-  const uint32_t la = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(uintptr_t)((__attribute__((address_space(3))) bf16_t*)lds));
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(la) : "memory", "m0");
-}
-#pragma clang diagnostic pop
 // 16 rows of a row-major (., CM_D) bf16 weight (src: the first row at k0), k0 ..
 // k0 + 31, into 16 slot rows of 64 B at dst (one piece)
 // row quad q -> chunk XOR 0, 2, 3, 1: quads {0, 3} of chunk g and {1, 2} of
@@ -143,7 +133,7 @@ __device__ __forceinline__ void cm_dma(const bf16_t* src, bf16_t* lds) {
 __device__ __forceinline__ int cm_q(int q) { return ((((q ^ (q >> 1)) & 1) << 1) | (q >> 1)) & 3; }
 __device__ __forceinline__ void cm_dma16(const bf16_t* src, bf16_t* dst, int lane) {
   const int r = lane >> 2, lc = (lane & 3) ^ cm_q((r >> 2) & 3);
-  cm_dma(src + (long long)r * CM_D + 8 * lc, dst);
+  lds_dma16(src + (long long)r * CM_D + 8 * lc, lds_addr(dst));
 }
 // fragment of slot row `row`, logical chunk g (8 consecutive k)
 __device__ __forceinline__ bf16x8 cm_frag(const bf16_t* slot, int row, int g) {

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "gemm256.h"
+#include "lds_dma.h"
 #include "mfma.h"
 #include "mx.h"
 
@@ -56,10 +57,6 @@ constexpr int kbuf() { return 4 * HALF + (MX ? SCB : 0); }
 template <bool MX>
 constexpr int lds_bytes() { return 2 * kbuf<MX>() > EPI_BYTES ? 2 * kbuf<MX>() : EPI_BYTES; }
 
-// one 1-KB LDS-DMA piece: lane l's 16 source bytes land at lds_wave + 16 l
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_wave) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_wave) : "memory", "m0");
-}
 // a dword piece: lane l's 4 bytes land at lds_wave + 4 l (exec-masked lanes write nothing)
 __device__ __forceinline__ void dma4(const void* src, uint32_t lds_wave) {
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" ::"v"(src), "s"(lds_wave) : "memory", "m0");
@@ -210,12 +207,12 @@ __global__ void __launch_bounds__(NT, 1) gemm256_kernel(G256 p) {
   auto issue_a1 = [&](int kt, int buf, int h) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      dma16(asrc[h][i] + kt * 128, __builtin_amdgcn_readfirstlane(lds0 + buf * KB + h * HALF + (2 * w + i) * 1024));
+      lds_dma16(asrc[h][i] + kt * 128, __builtin_amdgcn_readfirstlane(lds0 + buf * KB + h * HALF + (2 * w + i) * 1024));
   };
   auto issue_w1 = [&](int kt, int buf, int h) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      dma16(wsrc[h][i] + kt * 128,
+      lds_dma16(wsrc[h][i] + kt * 128,
             __builtin_amdgcn_readfirstlane(lds0 + buf * KB + (2 + h) * HALF + (2 * w + i) * 1024));
   };
   // scale dwords: A rows at 4*HALF + 4 r, W rows at 4*HALF + 1024 + 4 r

@@ -22,6 +22,27 @@ typedef uint16_t bf16_t;  // bf16 storage
 template <typename T>
 struct MT;
 
+// k-transposed bf16 fragment from a row-major [k][ld] tile X in LDS: the
+// operand rows are X's columns dbase + (lane & 15), the 8 k are
+// {k0 + 4g .. k0 + 4g + 3} ∪ {k0 + 16 + 4g .. +3}.  Two transposing reads
+// (ds_read_b64_tr_b16): lane 4q+p of each 16-lane group addresses row q,
+// columns 4p..4p+3 of the block.  swz(row) is XORed onto the row's 16-B chunk
+// index (it must be equal for rows r and r + 16); NoSwizzle: plain rows.
+struct NoSwizzle {
+  __device__ __forceinline__ int operator()(int) const { return 0; }
+};
+template <typename Swz = NoSwizzle>
+__device__ __forceinline__ bf16x8 frag_tr(const bf16_t* X, int ld, int k0, int dbase, int lane, Swz swz = Swz{}) {
+  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int r0 = k0 + 4 * g + q, col = dbase + 4 * p;
+  const bf16_t* a0 = X + r0 * ld + ((((col >> 3) ^ swz(r0)) << 3) | (col & 7));
+  const bf16_t* a1 = a0 + 16 * ld;
+  const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a0));
+  const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a1));
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
 template <>
 struct MT<bf16_t> {
   using frag = bf16x8;

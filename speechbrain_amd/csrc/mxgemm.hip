@@ -29,6 +29,7 @@
 //
 // Epilogue: bias, GELU / ReLU, alpha * val + fp32 residual, output fp32,
 // bf16 or MXFP8 (+ scales, amax over the 32 lanes of a tile row).
+#include "lds_dma.h"
 #include "mx.h"
 #include "gemm256.h"
 
@@ -262,10 +263,9 @@ constexpr int STAGE2 = BM2 * BK + BN * BK + SC2;
 constexpr int NSTAGE2 = 3;
 
 __device__ __forceinline__ void dma(const void* src, void* lds_wave, int bytes16) {
-  const uint32_t la = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(uintptr_t)((__attribute__((address_space(3))) uint8_t*)lds_wave));
+  const uint32_t la = lds_addr(lds_wave);
   if (bytes16)
-    asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(la) : "memory", "m0");
+    lds_dma16(src, la);
   else
     asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" ::"v"(src), "s"(la) : "memory", "m0");
 }
