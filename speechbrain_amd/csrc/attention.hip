@@ -500,6 +500,20 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
 //   B  V landed and every wave's S / G fragment reads are done -> read the
 //      scratch, then issue the next chunk's K / band, which land under the
 //      softmax and P·V.
+// The band is a ring of two 64-row segments in the 16 KB of Ps: segment s
+// holds band rows rbase0 + 64 s .. + 63 (rbase0 = Tn - QB - i0, rows clamped
+// to [0, 2 Tn - 2]) in half s & 1, and chunk c reads segments c and c + 1 (its
+// window row r is physical row (r + 64 (c & 1)) & 127).  The prologue stages
+// segments 0 and 1; after barrier B of chunk c only segment c + 2 is staged,
+// over segment c.  That needs no further barrier or wait: a wave passes B
+// only after its own lgkmcnt(0), so every wave's fragment reads of segment c
+// have returned before any wave issues the DMA that overwrites it, and the
+// vmcnt(0) + barrier of A in chunk c + 1 puts the new rows in front of that
+// chunk's reads, exactly as for K.  Segment c + 1 is not written while chunks
+// c and c + 1 read it.  Per chunk and workgroup the DMA moves 24 KB (K 8,
+// band 8, V 8; 32 KB when all 128 band rows were staged again), six pieces a
+// wave instead of eight.  (Staging the band twice cost 0.8 us of the 20.4 us
+// launch at B = 32, T = 376: profiles/attn_band_ring_timing.txt.)
 // Measured (s_memtime / s_memrealtime per workgroup, B = 32, T = 376,
 // profiles/r02_att_dma_timeline.log): all 768 workgroups start within 1 us
 // (one round, three per CU); a CU's three finish in turn at ~12.5 / 15.3 /
@@ -510,11 +524,13 @@ __global__ void __launch_bounds__(256, 2) relpos_flash_kernel(const T* __restric
 // The tiles are distinct __shared__ objects and the other LDS accesses come
 // before a DMA is issued, so the compiler's LDS-DMA alias guard (a vmcnt wait
 // before an LDS access it cannot tell apart from a DMA in flight) has little
-// to wait for.  50 KB of LDS and 144 VGPRs (76 without the band): three workgroups per CU.
+// to wait for.  50 KB of LDS and 158 VGPRs (76 without the band): three
+// workgroups per CU (168 VGPRs would still fit three waves per SIMD).
 namespace dmak {
 typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int RB = 64;   // bf16 per staged row (dh = 64): 128 B
-constexpr int PB = 128;  // band rows staged per chunk (127 used)
+constexpr int PB = 128;  // band rows a chunk reads (127 used): two segments of the ring
+constexpr int PSEG = 64;  // band rows per ring segment (= KC: the window moves one segment per chunk)
 constexpr int G2 = 72;   // G scratch row (floats): 18 16-B slots, ≡ 2 mod 4
 constexpr int GO = 4;    // scratch index of key 0 (spare slots GO - 1 and GO + KC)
 __device__ __forceinline__ int swz_kp(int row) { return (row >> 1) & 7; }
@@ -534,6 +550,10 @@ __device__ __forceinline__ void dma16(const bf16_t* src, bf16_t* lds) { lds_dma1
 // whose chunk time is VALU issue).
 __device__ __forceinline__ void dma16s(const void* sbase, uint32_t voff, uint32_t la) {
   asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(la) : "memory", "m0");
+}
+// LDS byte address of p, per lane (lds_addr is the wave-uniform form)
+__device__ __forceinline__ uint32_t lds_lane_addr(const void* p) {
+  return (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
 }
 // this wave's DMA pieces and LDS accesses done, then the workgroup barrier
 __device__ __forceinline__ void dma_barrier() {
@@ -576,32 +596,22 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
 
   // per-lane byte offsets of the interior-chunk DMA pieces (row stride x row
   // + swizzled 16-B chunk); the chunk's base goes in the scalar operand
-  uint32_t offk[2], offv[2], offp[4], lak[2], lav[2], lap[4];
+  uint32_t offk[2], offv[2], offp[2], lak[2], lav[2], lap[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r0 = 16 * w + 8 * i, row = r0 + lrow;
     offk[i] = (uint32_t)(row * row3 + ((lchk ^ swz_kp(row)) << 3)) * 2u;
     offv[i] = (uint32_t)(row * row3 + ((lchk ^ swz_v(row)) << 3)) * 2u;
+    offp[i] = BAND ? (uint32_t)(row * ldp + ((lchk ^ swz_kp(row)) << 3)) * 2u : 0u;
     lak[i] = lds_addr(Ks + r0 * RB);
     lav[i] = lds_addr(Vs + r0 * RB);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r0 = 32 * w + 8 * i, rr = r0 + lrow;
-    offp[i] = BAND ? (uint32_t)(rr * ldp + ((lchk ^ swz_kp(rr)) << 3)) * 2u : 0u;
     lap[i] = BAND ? lds_addr(Ps + r0 * RB) : 0u;
   }
-  auto dma_kp = [&](int j0) {
-    const int rbase = Tn - QB - i0 + j0;  // band row 0
-    if (j0 + KC <= Tn && (!BAND || (rbase >= 0 && rbase + PB <= 2 * Tn - 1))) {  // no row clamped
+  auto dma_k = [&](int j0) {
+    if (j0 + KC <= Tn) {  // no row clamped
       const bf16_t* sk = qkv_b + (long long)j0 * row3 + dh;
 #pragma unroll
       for (int i = 0; i < 2; ++i) dma16s(sk, offk[i], lak[i]);
-      if constexpr (BAND) {
-        const bf16_t* sp = pk_h + (long long)rbase * ldp;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dma16s(sp, offp[i], lap[i]);
-      }
       return;
     }
 #pragma unroll
@@ -609,12 +619,22 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
       const int r0 = 16 * w + 8 * i, row = r0 + lrow;
       dma16(qkv_b + (long long)min(j0 + row, Tn - 1) * row3 + dh + ((lchk ^ swz_kp(row)) << 3), Ks + r0 * RB);
     }
-    if constexpr (BAND)
+  };
+  // band segment sg (rows rbase0 + 64 sg .. + 63) into half `half` (= sg & 1)
+  // of the ring: this wave's rows 16w .. 16w+15 of the segment
+  auto dma_p = [&](int sg, int half) {
+    const int rb = Tn - QB - i0 + PSEG * sg;    // the segment's band row 0
+    if (rb >= 0 && rb + PSEG <= 2 * Tn - 1) {  // none of the 64 rows clamped
+      const bf16_t* sp = pk_h + (long long)rb * ldp;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {  // band rows 32w .. 32w+31
-      const int r0 = 32 * w + 8 * i, rr = r0 + lrow;
-      const int pr = min(max(rbase + rr, 0), 2 * Tn - 2);
-      dma16(pk_h + (long long)pr * ldp + ((lchk ^ swz_kp(rr)) << 3), Ps + r0 * RB);
+      for (int i = 0; i < 2; ++i) dma16s(sp, offp[i], lap[i] + half * (PSEG * RB * 2));
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int r0 = 16 * w + 8 * i, rr = r0 + lrow;
+      const int pr = min(max(rb + rr, 0), 2 * Tn - 2);
+      dma16(pk_h + (long long)pr * ldp + ((lchk ^ swz_kp(rr)) << 3), Ps + (half * PSEG + r0) * RB);
     }
   };
   auto dma_v = [&](int j0) {
@@ -635,7 +655,11 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
     g_att_wg[orig][0] = __builtin_amdgcn_s_memrealtime();
     g_att_wg[orig][2] = __builtin_amdgcn_s_memtime();
   })
-  dma_kp(0);
+  dma_k(0);
+  if constexpr (BAND) {
+    dma_p(0, 0);
+    dma_p(1, 1);
+  }
   const int nchunk = (Tn + KC - 1) / KC;  // <= 64 (launcher)
   // Key padding: which chunks hold a padded key, as a 64-bit chunk bitmap
   // built once (wave w scans chunks w, w + 4, ...; merged after barrier A of
@@ -689,8 +713,40 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
   f32x4 acc_o[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) acc_o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // This wave's G tile t reads window rows pofs + 16t + c16; in the ring that
+  // is physical row (row + 64 (ch & 1)) & 127.  A tile lies within one half
+  // (pofs is a multiple of 16), so an odd chunk moves it by + or - 64 rows
+  // wave-uniformly: tiles t <= w (first segment) up, the others down.  The
+  // chunk loop is unrolled by two and each copy reads through LDS addresses
+  // formed here, once: even chunks pa0[s] + 2048 t; odd chunks pa0[s] + 8192
+  // for tile 0 (always up), pa0[s] + 0 for tile 4 (always down) and the
+  // selected pa1[s][t - 1] for tiles 1..3.  swz_kp takes bits 1..3 of the row,
+  // i.e. of c16, in either half.  (Left as expressions of the row, the
+  // compiler re-added the odd chunk's ten addresses inside the loop.)
   const int pofs = 48 - 16 * w;
-  for (int ch = 0; ch < nchunk; ++ch) {
+  uint32_t pa0[2] = {0u, 0u}, pa1[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};
+  if constexpr (BAND)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      pa0[s] = lds_lane_addr(Ps + (pofs + c16) * RB + (((4 * s + g) ^ swz_kp(c16)) << 3));
+#pragma unroll
+      for (int t = 1; t < 4; ++t) {
+        pa1[s][t - 1] = pa0[s] + 2 * RB * (16 * t + (t <= w ? PSEG : -PSEG));
+        asm volatile("" : "+v"(pa1[s][t - 1]));  // kept in a register, not re-derived per chunk
+      }
+      asm volatile("" : "+v"(pa0[s]));
+    }
+  auto band_frag = [&](int par, int s, int t) {  // par, s, t: constants once unrolled
+    const bool odd = par != 0;
+    const uint32_t a = !odd ? pa0[s] + 2 * RB * 16 * t
+                            : t == 0 ? pa0[s] + 2 * RB * PSEG : t == 4 ? pa0[s] : pa1[s][t - 1];
+    return *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(a);
+  };
+  // BAND: two chunks per trip, so that par = ch & 1 is a constant in each copy
+  // BAND: two chunks per trip, so that par = ch & 1 is a constant in each copy
+  for (int ch = 0; ch < nchunk;)
+#pragma unroll
+  for (int par = 0; par < (BAND ? 2 : 1) && ch < nchunk; ++par, ++ch) {
     const int j0 = ch * KC;
     const bool more = ch + 1 < nchunk;
     dma_barrier();  // A
@@ -719,10 +775,7 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
       }
       if constexpr (BAND)
 #pragma unroll
-        for (int t = 0; t < 5; ++t) {
-          const int row = pofs + 16 * t + c16;
-          fpb[t] = *reinterpret_cast<const bf16x8*>(Ps + row * RB + (((4 * s + g) ^ swz_kp(row)) << 3));
-        }
+        for (int t = 0; t < 5; ++t) fpb[t] = band_frag(par, s, t);
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc_s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[t], fqu[s], acc_s[t], 0, 0, 0);
       if constexpr (BAND)
@@ -751,7 +804,10 @@ __global__ void __launch_bounds__(256, 3) relpos_flash_dma_kernel(const bf16_t* 
       gv[t] = BAND ? *reinterpret_cast<const f32x4*>(gq + 16 * t + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
     const bool chunk_padded = ((ch < 32 ? mlo >> ch : mhi >> (ch - 32)) & 1u) != 0u;
     __builtin_amdgcn_sched_barrier(0);
-    if (more) dma_kp(j0 + KC);
+    if (more) {
+      dma_k(j0 + KC);
+      if constexpr (BAND) dma_p(ch + 2, par);  // over segment ch: every wave read it before B
+    }
     float p[4][4];
     float cmax = -INFINITY;
     // S + G as packed fp32 pairs (v_pk_add_f32: half the instructions of the
