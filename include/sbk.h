@@ -1017,6 +1017,67 @@ int sbk_ligru_bwd(int bf16, int D, int act, const void* uT, const float* hx, con
                   const float* mask, const float* dy, int B, int T, int H, float* dG, float* dhw, float* dhx,
                   void* stream);
 
+/* ---- attdec.hip: attentional GRU decoder steps (nnet/RNN.py:713-958, nnet/attention.py:23-234) ---- */
+
+/* Frames of one score workgroup: nt = ceil(L / sbk_attdec_tile()) sizes the scratch below. */
+int sbk_attdec_tile(void);
+
+/* The T forward steps of AttentionalRNNDecoder(rnn_type "gru", one layer)
+ * with content-based (w_loc null) or location-aware attention, five launches
+ * per step: GRU cell on x_t = [inp_t | c_{t-1}], query, score + tile softmax
+ * share, combine, context projection.  Sizes: H hidden, A attn_dim, O the
+ * width of the context c (= A in the decoder), E enc_dim, C conv channels
+ * (<= 64), ksz the reference's kernel_size (2 * ksz + 1 taps), L frames.
+ * bf16 != 0: w_ic, w_hh, w_dec, w_out are bf16 and their fp32 state operands
+ * are rounded at the MFMA; else fp32 and exact-fp32 MFMA.  Everything else is
+ * fp32 in both modes.
+ *   w_ic (3H, O) = W_ih[:, I:], w_hh (3H, H), b_hh (3H) or null; gate order r, z, n
+ *   w_dec (A, H); b_q (A) or null, added to the query (b_dec + b_loc)
+ *   w_out (O, E), b_out (O) or null
+ *   gx (B, T, 3H) = (inp * mask) W_ih[:, :I]^T + b_ih
+ *   mc (B, T, O) or null: the dropout keep-mask of c; row t multiplies c_{t-1}
+ *     (c0 arrives already multiplied by row 0)
+ *   P (B, L, A) = enc W_enc^T + b_enc; enc (B, L, E); enc_len (B) int32 in [1, L]
+ *   w_conv (C, 2 ksz + 1), w_loc (A, C): both or neither; w_attn (A); scaling
+ *   h0 (B, H), c0 (B, O) or null (zeros); attn0 (B, L): prev_attn of step 0
+ *     (location only; the reference starts from mask / enc_len)
+ * Writes hstate (B, T, H), cstate (B, T, O), ctx (B, T, E) = attn . enc, attn
+ * (B, T, L) (exactly zero at frames >= enc_len), dech (B, T, A) and, unless
+ * null, save (B, T, 4, H) = r, z, n, W_hn h + b_hn.  ws: B * (O + L + nt * (2 + E))
+ * floats of scratch.  w_hh null: attention only — T must be 1, hstate (B, H)
+ * is the query's input, w_ic / gx / mc must be null.  A null required
+ * pointer, a size <= 0, B > 65535, C > 64, one of w_conv / w_loc without the
+ * other, a staging area past the LDS: 1001, before any launch.  No atomics. */
+int sbk_attdec_fwd(int bf16, const void* w_ic, const void* w_hh, const float* b_hh, const void* w_dec,
+                   const float* b_q, const void* w_out, const float* b_out, const float* gx, const float* mc,
+                   const float* P, const float* enc, const int* enc_len, const float* w_conv, const float* w_loc,
+                   const float* w_attn, float scaling, const float* h0, const float* c0, const float* attn0, int B,
+                   int T, int L, int H, int A, int O, int E, int C, int ksz, float* hstate, float* cstate, float* ctx,
+                   float* attn, float* dech, float* save, float* ws, void* stream);
+
+/* The backward steps t = T-1 .. 0, five launches each.  w_icT (O, 3H), w_hhT
+ * (H, 3H), w_decT (H, A), w_outT (E, O): the transposes, in the compute
+ * dtype.  P .. save as given to / written by sbk_attdec_fwd.  dattn (B, T, L)
+ * or null: the gradient arriving on attn; dhproj (B, T, H): the gradient
+ * arriving on every h_t from outside the recurrence.  dcall (B, T, O) holds
+ * the same for every c_t on entry and the full dC_t on return.  Writes dgi,
+ * dgh = (dr, dz, dn * r) (B, T, 3H), dctx (B, T, E), ddech (B, T, A) (the
+ * gradient of the query, biases included); adds to dP (B, L, A) and to slots
+ * (B * nt, A + A * C + C * (2 ksz + 1)) = per score workgroup the sums of
+ * dw_attn, dW_loc, dw_conv over the steps — both zeroed by the caller, the
+ * slots reduced by it afterwards (C counts as 0 when w_loc is null).
+ * prev_attn is detached as in the reference: no gradient flows through the
+ * location features into earlier steps, nor into h0 / c0 / attn0.  ws:
+ * 2 * B * H + B * nt * A floats of scratch.  Errors as sbk_attdec_fwd.  No
+ * atomics. */
+int sbk_attdec_bwd(int bf16, const void* w_icT, const void* w_hhT, const void* w_decT, const void* w_outT,
+                   const float* P, const float* enc, const int* enc_len, const float* w_conv, const float* w_loc,
+                   const float* w_attn, float scaling, const float* h0, const float* attn0, const float* mc,
+                   const float* hstate, const float* ctx, const float* attn, const float* dech, const float* save,
+                   const float* dattn, const float* dhproj, int B, int T, int L, int H, int A, int O, int E, int C,
+                   int ksz, float* dcall, float* dgi, float* dgh, float* dctx, float* dP, float* ddech, float* slots,
+                   float* ws, void* stream);
+
 /* ------------------------------------------- time-domain augmentation */
 
 /* csrc/tdaug.hip: the waveform stage of the reference's

@@ -25,10 +25,15 @@ CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-a
           "-Wno-unused-result", "-fvisibility=hidden", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 
 
+# per-source additions: attdec.hip is compiled without the packed fp32 VALU
+# forms (v_pk_add/mul/fma_f32), so its epilogues are scalar fp32 throughout
+EXTRA = {"attdec.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _flags_changed():
     """Objects are rebuilt when the compile flags change (stamp under build/)."""
     stamp = os.path.join(OBJ, "flags.txt")
-    want = " ".join([HIPCC] + CFLAGS)
+    want = " ".join([HIPCC] + CFLAGS + [f"{k}:{' '.join(v)}" for k, v in sorted(EXTRA.items())])
     have = open(stamp).read() if os.path.exists(stamp) else ""
     if have != want:
         os.makedirs(OBJ, exist_ok=True)
@@ -43,7 +48,7 @@ def _compile(src, force=False):
     deps = [src] + glob.glob(os.path.join(CSRC, "*.h"))
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(d) for d in deps):
         return obj, None
-    cmd = [HIPCC, *CFLAGS, "-c", src, "-o", obj]
+    cmd = [HIPCC, *CFLAGS, *EXTRA.get(os.path.basename(src), []), "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         return obj, f"{' '.join(cmd)}\n{r.stdout}\n{r.stderr}"

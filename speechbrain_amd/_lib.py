@@ -167,6 +167,10 @@ SIGNATURES = {
     # ligru.hip (LiGRU recurrence, both directions in one launch per step, shared weights)
     "sbk_ligru_fwd": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "sbk_ligru_bwd": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    # attdec.hip (attentional GRU decoder: cell, query, score, combine, projection per step)
+    "sbk_attdec_tile": [],
+    "sbk_attdec_fwd": [_i] + [_vp] * 15 + [_f] + [_vp] * 3 + [_i] * 9 + [_vp] * 8,
+    "sbk_attdec_bwd": [_i] + [_vp] * 10 + [_f] + [_vp] * 10 + [_i] * 9 + [_vp] * 9,
     # attention.hip
     "sbk_relpos_attention":[_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],

@@ -619,3 +619,145 @@ class LSTM(_Recurrent):
             if layer < L - 1 and rnn.dropout > 0:
                 y = A.dropout(y, rnn.dropout, self.training)
         return y, (torch.cat(hns, 0), torch.cat(cns, 0))
+
+
+class GRUCell(torch.nn.Module):
+    """Drop-in for speechbrain.nnet.RNN.GRUCell (RNN.py:498-600): same
+    constructor, `rnn_cells` (torch.nn.GRUCell parameter holders, never
+    called) and forward(x (B, fea), hx=None) -> (h, hidden (layers, B, H)).
+    Each layer is one step of the GRU layer above (input GEMM + one launch of
+    csrc/gru.hip)."""
+
+    def __init__(self, hidden_size, input_shape=None, input_size=None, num_layers=1, bias=True, dropout=0.0,
+                 re_init=True):
+        super().__init__()
+        self.hidden_size = hidden_size
+        self.num_layers = num_layers
+        if input_shape is None and input_size is None:
+            raise ValueError("Expected one of input_shape or input_size.")
+        if input_size is None:
+            if len(input_shape) > 3:
+                self.reshape = True
+            input_size = torch.prod(torch.tensor(input_shape[1:]))
+        kwargs = {"input_size": input_size, "hidden_size": self.hidden_size, "bias": bias}
+        self.rnn_cells = torch.nn.ModuleList([torch.nn.GRUCell(**kwargs)])
+        kwargs["input_size"] = self.hidden_size
+        for _ in range(self.num_layers - 1):
+            self.rnn_cells.append(torch.nn.GRUCell(**kwargs))
+        self.dropout_layers = torch.nn.ModuleList([torch.nn.Dropout(p=dropout) for _ in range(self.num_layers - 1)])
+        if re_init:
+            rnn_init(self.rnn_cells)
+        self._wc = _enc.WeightCache()
+
+    def forward(self, x, hx=None):
+        require_device(x, hx, self.rnn_cells[0].weight_hh)
+        dtype = _enc.compute_dtype()
+        h, hidden = x, []
+        for i, cell in enumerate(self.rnn_cells):
+            if i > 0:
+                h = A.dropout(h, self.dropout_layers[i - 1].p, self.training)
+            _, h = _GRULayerFn.apply(h.unsqueeze(1), None, 0, cell.weight_ih, cell.weight_hh,
+                                     getattr(cell, "bias_ih", None), getattr(cell, "bias_hh", None),
+                                     None if hx is None else hx[i], None, dtype, self._wc, f"c{i}")
+            hidden.append(h)
+        return h, torch.stack(hidden, dim=0)
+
+
+class AttentionalRNNDecoder(torch.nn.Module):
+    """Drop-in for speechbrain.nnet.RNN.AttentionalRNNDecoder (RNN.py:713-958)
+    for rnn_type "gru", num_layers 1 and attn_type "location" / "content" (the
+    `dec:` of the seq2seq recipes): same constructor, attributes, state_dict,
+    forward(inp_tensor, enc_states, wav_len) -> (outputs (B, T, H), attn
+    (B, T, L)) and forward_step(inp, hs, c, enc_states, enc_len) -> (dec_out,
+    hs, c, w).  Other rnn / attention types and num_layers > 1 raise
+    NotImplementedError at construction.
+
+    forward runs the step kernels of csrc/attdec.hip (five launches per token,
+    forward and backward) between the GEMMs that do not depend on the
+    recurrence: mlp_enc over all frames and the input half of W_ih over all
+    tokens before the loop, proj over all tokens after it.
+
+    Dropout (`self.drop` on cat[inp, c], training, p > 0): the keep-masks of
+    all steps are drawn before the loop in one
+    torch.nn.functional.dropout(torch.ones(B, T, I + A, device=...), p) call;
+    the reference draws (B, I + A) per step, so under the same seed the masks
+    differ while their distribution does not.  forward_step draws its own
+    (B, I + A) mask and is grad-free (the searchers' entry point)."""
+
+    def __init__(self, rnn_type, attn_type, hidden_size, attn_dim, num_layers, enc_dim, input_size,
+                 nonlinearity="relu", re_init=True, normalization="batchnorm", scaling=1.0, channels=None,
+                 kernel_size=None, bias=True, dropout=0.0):
+        super().__init__()
+        from .attention import ContentBasedAttention, LocationAwareAttention
+        self.rnn_type = rnn_type.lower()
+        self.attn_type = attn_type.lower()
+        self.hidden_size = hidden_size
+        self.attn_dim = attn_dim
+        self.num_layers = num_layers
+        self.scaling = scaling
+        self.bias = bias
+        self.dropout = dropout
+        self.normalization = normalization
+        self.re_init = re_init
+        self.nonlinearity = nonlinearity
+        self.channels = channels
+        self.kernel_size = kernel_size
+        if self.rnn_type not in ("rnn", "gru", "lstm"):
+            raise ValueError(f"{self.rnn_type} not implemented.")
+        if self.attn_type not in ("content", "location", "keyvalue"):
+            raise ValueError(f"{self.attn_type} is not implemented.")
+        if self.rnn_type != "gru" or self.attn_type == "keyvalue" or num_layers != 1:
+            raise NotImplementedError("speechbrain_amd AttentionalRNNDecoder has kernels for rnn_type='gru', "
+                                      "num_layers=1, attn_type 'location' / 'content' "
+                                      f"(got {self.rnn_type!r}, {num_layers}, {self.attn_type!r})")
+        self.proj = torch.nn.Linear(self.hidden_size + self.attn_dim, self.hidden_size)
+        if self.attn_type == "content":
+            self.attn = ContentBasedAttention(enc_dim=enc_dim, dec_dim=self.hidden_size, attn_dim=self.attn_dim,
+                                              output_dim=self.attn_dim, scaling=self.scaling)
+        else:
+            self.attn = LocationAwareAttention(enc_dim=enc_dim, dec_dim=self.hidden_size, attn_dim=self.attn_dim,
+                                               output_dim=self.attn_dim, conv_channels=self.channels,
+                                               kernel_size=self.kernel_size, scaling=self.scaling)
+        self.drop = torch.nn.Dropout(p=self.dropout)
+        self.rnn = GRUCell(input_size=input_size + self.attn_dim, hidden_size=self.hidden_size,
+                           num_layers=self.num_layers, bias=self.bias, dropout=0, re_init=self.re_init)
+        self._wc = _enc.WeightCache()
+
+    def forward_step(self, inp, hs, c, enc_states, enc_len):
+        from .. import _attdec
+        require_device(inp, c, enc_states, self.proj.weight)
+        if A.needs_grad(inp, c, enc_states, self) or (hs is not None and A.needs_grad(hs)):
+            raise NotImplementedError("forward_step has no backward: call it under torch.no_grad() "
+                                      "(forward is the differentiable path)")
+        at = self.attn
+        if at.precomputed_enc_h is None:
+            at._start(enc_states, enc_len)
+        c = c.detach().float()
+        if self.training and self.drop.p > 0:
+            m = torch.nn.functional.dropout(torch.ones(inp.shape[0], inp.shape[1] + c.shape[1], device=inp.device),
+                                            self.drop.p)
+            inp, c = inp * m[:, :inp.shape[1]], c * m[:, inp.shape[1]:]
+        h0 = None if hs is None else hs[0].detach().float().contiguous()
+        out, h, c, w = _attdec.step(self, inp, h0, c.contiguous(), at.precomputed_enc_h, enc_states, at._len32,
+                                    at._prev())
+        at._keep(w)
+        return out, h.unsqueeze(0), c, w
+
+    def forward(self, inp_tensor, enc_states, wav_len):
+        from .. import _attdec
+        require_device(inp_tensor, enc_states, wav_len, self.proj.weight)
+        B, T, I = inp_tensor.shape
+        enc_len = torch.round(enc_states.shape[1] * wav_len).long()
+        at = self.attn
+        at.reset()
+        at._start(enc_states, enc_len, precompute=False)
+        mask = None
+        if self.training and self.drop.p > 0:
+            mask = torch.nn.functional.dropout(torch.ones(B, T, I + self.attn_dim, device=inp_tensor.device),
+                                               self.drop.p)
+        outputs, attn, P = _attdec.AttDecFn.apply(inp_tensor, enc_states, at._len32, mask, at._prev(), self.scaling,
+                                                  _enc.compute_dtype(), self._wc, *_attdec.weights_of(self))
+        # the state the reference's loop leaves behind
+        at.precomputed_enc_h = P
+        at._keep(attn[:, -1])
+        return outputs, attn

@@ -7,6 +7,14 @@ linear_pos GEMM → one fused rel-pos attention kernel (scores, closed-form
 rel_shift, mask, softmax, P·V) → out_proj GEMM.  With query != key / value
 (any q_len, k_len) it runs separate q / k / v GEMMs → the cross-length
 rel-pos core of csrc/xattn.hip → out_proj, forward and backward.
+
+ContentBasedAttention and LocationAwareAttention (attention.py:23-234) are
+the attention of AttentionalRNNDecoder (nnet/RNN.py): the parameter holders
+and the `reset()` / `precomputed_enc_h` / `mask` / `prev_attn` state of the
+reference.  Inside the decoder's forward they run as part of its step
+kernels (csrc/attdec.hip), forward and backward; called on their own (what a
+searcher does, one step at a time) they run the query, score, combine and
+projection launches of one step, without gradients.
 """
 import math
 
@@ -17,7 +25,8 @@ from .. import _autograd as A
 from .. import _enc
 from .activations import Swish
 
-__all__ = ["RelPosEncXL", "RelPosMHAXL", "PositionalwiseFeedForward", "MultiheadAttention"]
+__all__ = ["RelPosEncXL", "RelPosMHAXL", "PositionalwiseFeedForward", "MultiheadAttention", "ContentBasedAttention",
+           "LocationAwareAttention"]
 
 # head size limit of the fused self-attention kernels (csrc/attention.hip);
 # wider heads take the xattn core (dh <= 256), as any cross-attention does
@@ -550,3 +559,89 @@ def _mode_weight(w, mode):
     if mode == torch.bfloat16:
         return _enc.cast_bf16(w.float().contiguous())
     return w.float().contiguous()
+
+
+class ContentBasedAttention(nn.Module):
+    """attention.py:23-107: same constructor, parameters and
+    forward(enc_states, enc_len, dec_states) -> (context, attn)."""
+
+    def __init__(self, enc_dim, dec_dim, attn_dim, output_dim, scaling=1.0):
+        super().__init__()
+        self.mlp_enc = nn.Linear(enc_dim, attn_dim)
+        self.mlp_dec = nn.Linear(dec_dim, attn_dim)
+        self.mlp_attn = nn.Linear(attn_dim, 1, bias=False)
+        self._init_location()
+        self.mlp_out = nn.Linear(enc_dim, output_dim)
+        self.scaling = scaling
+        self.softmax = nn.Softmax(dim=-1)
+        self._wc = _enc.WeightCache()
+        self.reset()
+
+    def _init_location(self):
+        pass
+
+    def reset(self):
+        self.enc_len = None
+        self.precomputed_enc_h = None
+        self.mask = None
+        self._len32 = None
+
+    def _start(self, enc_states, enc_len, precompute=True):
+        """The per-utterance state: lengths, mask and (unless the caller fills it in) mlp_enc(enc_states)."""
+        from .. import _attdec
+        L = enc_states.shape[1]
+        self.enc_len = enc_len
+        self._len32 = enc_len.to(device=enc_states.device, dtype=torch.int32)
+        if precompute:
+            self.precomputed_enc_h = _attdec.precompute(enc_states, self.mlp_enc.weight, self.mlp_enc.bias,
+                                                        _enc.compute_dtype(), self._wc)
+        self.mask = (torch.arange(L, device=enc_states.device)[None, :] < self._len32[:, None]).float()
+
+    def _prev(self):
+        return None
+
+    def _keep(self, attn):
+        pass
+
+    def forward(self, enc_states, enc_len, dec_states):
+        from .. import _attdec
+        from .._lib import require_device
+        require_device(enc_states, dec_states, self.mlp_enc.weight)
+        if A.needs_grad(enc_states, dec_states, self):
+            raise NotImplementedError("a standalone attention call has no backward: call it under torch.no_grad() "
+                                      "(AttentionalRNNDecoder.forward is the differentiable path)")
+        if self.precomputed_enc_h is None:
+            self._start(enc_states, enc_len)
+        context, attn = _attdec.attend(self, enc_states, dec_states, self._prev())
+        self._keep(attn)
+        return context, attn
+
+
+class LocationAwareAttention(ContentBasedAttention):
+    """attention.py:110-234: same constructor, parameters (the reference's
+    construction order, so a seeded construction gives its weights) and
+    forward; `prev_attn` carries the previous weights between calls."""
+
+    def __init__(self, enc_dim, dec_dim, attn_dim, output_dim, conv_channels, kernel_size, scaling=1.0):
+        self._loc_cfg = (conv_channels, kernel_size, attn_dim)
+        super().__init__(enc_dim, dec_dim, attn_dim, output_dim, scaling)
+
+    def _init_location(self):
+        C, k, attn_dim = self._loc_cfg
+        self.conv_loc = nn.Conv1d(1, C, kernel_size=2 * k + 1, padding=k, bias=False)
+        self.mlp_loc = nn.Linear(C, attn_dim)
+        self.mlp_attn = nn.Linear(attn_dim, 1, bias=False)   # the reference builds it twice
+
+    def reset(self):
+        super().reset()
+        self.prev_attn = None
+
+    def _start(self, enc_states, enc_len, precompute=True):
+        super()._start(enc_states, enc_len, precompute)
+        self.prev_attn = self.mask * (1 / self._len32.float()).unsqueeze(1)
+
+    def _prev(self):
+        return self.prev_attn.contiguous()
+
+    def _keep(self, attn):
+        self.prev_attn = attn.detach()
