@@ -1078,6 +1078,41 @@ int sbk_attdec_bwd(int bf16, const void* w_icT, const void* w_hhT, const void* w
                    int ksz, float* dcall, float* dgi, float* dgh, float* dctx, float* dP, float* ddech, float* slots,
                    float* ws, void* stream);
 
+/* Hypotheses of one beam-score workgroup (one MFMA row tile): the score grid of
+ * sbk_attdec_beam_step is (nt, B, ceil(G / sbk_attdec_beam_group())). */
+int sbk_attdec_beam_group(void);
+
+/* One decoder step of a beam search over N = B * G hypotheses (row n = b * G
+ * + g) that share the B utterances' enc (B, L, E), P (B, L, A) and enc_len
+ * (B): nothing is inflated.  Row n continues row parent[n] (int32, inside its
+ * own utterance; a value outside is held to the utterance's rows) of the
+ * previous step: h_prev (N, H), c_prev (N, O), attn_prev (N, L; location
+ * only), cov_prev (N, L) and peak_prev (N) int32 are read at parent[n], and h,
+ * c, attn, cov, peak are written at n — two buffers that the caller swaps.
+ * Five launches, stream order between them: the GRU cell with h and c gathered
+ * (its input half is row token[n] of the table gx (V, 3H) = emb W_ih[:, :I]^T
+ * + b_ih, or row n of gx (N, 3H) when token is null), the query, the
+ * beam-grouped score (P, W_loc, w_attn and enc read once per kGH hypotheses),
+ * the combine, the context projection.  Weights, sizes, scaling and bf16 as
+ * sbk_attdec_fwd.  The combine also writes peak[n] = the first index of
+ * attn[n]'s maximum, shift_ok[n] = (peak[n] <= peak_prev[parent[n]] +
+ * max_shift && peak[n] > peak_prev[parent[n]] - max_shift), cov[n] =
+ * cov_prev[parent[n]] + attn[n] (2 attn[n] when first != 0: the reference
+ * initialises its coverage with the step's attention and then adds it) and
+ * pen[n] = sum_l max(cov[n][l], 0.5) - 0.5 L over all L frames.  attn is
+ * exactly zero at frames >= enc_len.  ctx (N, E) and dech (N, A) are written
+ * on the way; ws: N * (L + nt * (2 + E)) floats of scratch.  Errors as
+ * sbk_attdec_fwd, also for B * G > 65535 or max_shift outside [0, 2^30]:
+ * 1001, before any launch.  No atomics. */
+int sbk_attdec_beam_step(int bf16, const void* w_ic, const void* w_hh, const float* b_hh, const void* w_dec,
+                         const float* b_q, const void* w_out, const float* b_out, const float* gx, const int* token,
+                         const float* P, const float* enc, const int* enc_len, const float* w_conv,
+                         const float* w_loc, const float* w_attn, float scaling, const int* parent,
+                         const float* h_prev, const float* c_prev, const float* attn_prev, const float* cov_prev,
+                         const int* peak_prev, int first, int max_shift, int V, int B, int G, int L, int H, int A,
+                         int O, int E, int C, int ksz, float* h, float* c, float* attn, float* cov, int* peak,
+                         int* shift_ok, float* pen, float* ctx, float* dech, float* ws, void* stream);
+
 /* ------------------------------------------- time-domain augmentation */
 
 /* csrc/tdaug.hip: the waveform stage of the reference's

@@ -171,6 +171,8 @@ SIGNATURES = {
     "sbk_attdec_tile": [],
     "sbk_attdec_fwd": [_i] + [_vp] * 15 + [_f] + [_vp] * 3 + [_i] * 9 + [_vp] * 8,
     "sbk_attdec_bwd": [_i] + [_vp] * 10 + [_f] + [_vp] * 10 + [_i] * 9 + [_vp] * 9,
+    "sbk_attdec_beam_group": [],
+    "sbk_attdec_beam_step": [_i] + [_vp] * 15 + [_f] + [_vp] * 6 + [_i] * 12 + [_vp] * 11,
     # attention.hip
     "sbk_relpos_attention":[_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "sbk_relpos_attention_lds": [_i, _i, _i],

@@ -637,6 +637,353 @@ __global__ void __launch_bounds__(kThreads) cell_bwd_kernel(BwdArgs a, int t) {
   }
 }
 
+// ------------------------------------------------- beam-grouped decode step
+// One step over N = B * G hypotheses (row n = b * G + g) that share the B
+// utterances' enc, P and enc_len.  Row n continues row parent[n] of the
+// previous step: every per-row operand is read through parent from one buffer
+// and written at n into the other, so a beam permutation moves no state.
+
+constexpr int kGH = 16;   // hypotheses of a score workgroup: one MFMA row tile
+
+struct BeamArgs {
+  const void *w_ic, *w_hh;                    // (3H, O), (3H, H) in the compute dtype
+  const float *b_hh, *gx;                     // (3H) or null; (V, 3H) table with token, else (N, 3H)
+  const int* token;                           // (N) or null
+  const float *P, *enc;                       // (B, L, A), (B, L, E)
+  const int* enc_len;                         // (B)
+  const float *w_conv, *w_loc, *w_attn;
+  const int* parent;                          // (N)
+  const float *h_prev, *c_prev, *attn_prev, *cov_prev;  // (N, H | O | L | L)
+  const int* peak_prev;                       // (N)
+  const float* dech;                          // (N, A)
+  float *h, *attn, *cov, *ctx, *pen;          // (N, H | L | L | E), (N)
+  int *peak, *shift_ok;                       // (N)
+  float *scores, *ms, *pctx;                  // (N, L), (N, nt, 2), (N, nt, E)
+  float scaling;
+  int first, max_shift, V;
+  int B, G, N, L, H, A, O, E, C, ksz, nt;
+  int vec_ic, vec_hh, vec_c, vec_h;
+};
+
+// the row that row n continues, held inside n's utterance
+__device__ __forceinline__ int parent_row(const int* parent, int n, int G) {
+  const int lo = n / G * G, p = parent[n];
+  return p < lo ? lo : (p >= lo + G ? lo + G - 1 : p);
+}
+
+// rnnstep.h's product with the rows of X mapped: tile row 16 m + (lane & 15)
+// reads X row src[m] (none when negative)
+template <typename T, int G>
+__device__ __forceinline__ void product_rows(f32x4 (&out)[kMT][G], const T* W, int gate_rows, int K, const float* X,
+                                             long long ldx, const int (&src)[kMT], int j0, int H, int mts, bool vec_w,
+                                             bool vec_x, int lane, int w) {
+  f32x4 acc[kMT][G];
+#pragma unroll
+  for (int m = 0; m < kMT; ++m)
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[m][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int unit = j0 + (lane & 15);
+#pragma unroll 2
+  for (int k0 = w * 32; k0 < K; k0 += kWaves * 32) {
+    const int kk = k0 + 8 * (lane >> 4);
+    typename MT<T>::frag bw[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+      bw[g] = unit < H ? load_w8<T>(W + ((long long)g * gate_rows + unit) * K, kk, K, vec_w) : MT<T>::zero();
+#pragma unroll
+    for (int m = 0; m < kMT; ++m) {
+      if (m < mts) {
+        const typename MT<T>::frag af = src[m] >= 0 ? load_f8<T>(X + src[m] * ldx, kk, K, vec_x) : MT<T>::zero();
+#pragma unroll
+        for (int g = 0; g < G; ++g) MT<T>::mma(acc[m][g], af, bw[g]);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < kMT; ++m)
+#pragma unroll
+    for (int g = 0; g < G; ++g) out[m][g] = acc[m][g];
+}
+
+// cell_fwd_kernel with h and c gathered through parent and the input half of
+// the gates read from row token[n] of the (V, 3H) table
+template <typename T>
+__global__ void __launch_bounds__(kThreads) beam_cell_kernel(BeamArgs a) {
+  __shared__ float red[kWaves][4][kRows][kSlice];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int H = a.H, N = a.N, O = a.O;
+  const int j0 = blockIdx.x * kSlice, b0 = blockIdx.y * kRows;
+  const int nrows = N - b0 < kRows ? N - b0 : kRows;
+  const int mts = (nrows + 15) >> 4;
+  int src[kMT];
+#pragma unroll
+  for (int m = 0; m < kMT; ++m) {
+    const int row = b0 + m * 16 + (lane & 15);
+    src[m] = row < N ? parent_row(a.parent, row, a.G) : -1;
+  }
+  f32x4 ai[kMT][3], ah[kMT][3], acc[kMT][4];
+  product_rows<T, 3>(ai, static_cast<const T*>(a.w_ic), H, O, a.c_prev, O, src, j0, H, mts, a.vec_ic, a.vec_c, lane, w);
+  product_rows<T, 3>(ah, static_cast<const T*>(a.w_hh), H, H, a.h_prev, H, src, j0, H, mts, a.vec_hh, a.vec_h, lane, w);
+#pragma unroll
+  for (int m = 0; m < kMT; ++m) {
+    acc[m][0] = ai[m][0] + ah[m][0];
+    acc[m][1] = ai[m][1] + ah[m][1];
+    acc[m][2] = ai[m][2];
+    acc[m][3] = ah[m][2];
+  }
+  meet<4>(red, acc, mts, lane, w);
+
+  const long long H3 = 3LL * H;
+  for (int e = tid; e < nrows * kSlice; e += kThreads) {
+    const int rr = e >> 4, jj = e & 15;
+    const int n = b0 + rr, j = j0 + jj;
+    if (j >= H) continue;
+    float s[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) s[g] = total<4>(red, g, rr, jj);
+    const float br = a.b_hh ? a.b_hh[j] : 0.f, bz = a.b_hh ? a.b_hh[H + j] : 0.f, bn = a.b_hh ? a.b_hh[2 * H + j] : 0.f;
+    int xrow = n;
+    if (a.token) {
+      const int v = a.token[n];
+      xrow = v < 0 ? 0 : (v >= a.V ? a.V - 1 : v);
+    }
+    const float* gx = a.gx + xrow * H3;
+    const float hp = a.h_prev[(long long)parent_row(a.parent, n, a.G) * H + j];
+    const float r = sigmoid_exact(gx[j] + (s[0] + br));
+    const float z = sigmoid_exact(gx[H + j] + (s[1] + bz));
+    const float q = s[3] + bn;
+    const float nn = tanhf(gx[2 * H + j] + s[2] + r * q);
+    a.h[(long long)n * H + j] = (1.f - z) * nn + z * hp;
+  }
+}
+
+// floats of the group's staging area: taps, kGH windows, kGH location-feature tiles
+__host__ __device__ inline int beam_stage_floats(int C, int ksz) {
+  return C ? C * (2 * ksz + 1) + kGH * (kLT + 2 * ksz) + kGH * kLT * cq_of(C) : 0;
+}
+
+// sum over the 16 lanes of an MFMA tile row on DPP row permutes (no LDS round trip)
+__device__ __forceinline__ float row16_sum_v(float v) {
+  v += dpp_f32<0x140>(v);
+  v += dpp_f32<0x141>(v);
+  v += dpp_f32<0x4E>(v);
+  v += dpp_f32<0xB1>(v);
+  return v;
+}
+
+// Grid (ceil(L / 32), B, ceil(G / kGH)).  The workgroup owns 32 frames of one
+// utterance and up to kGH of its hypotheses.  Staged once: the taps; per
+// hypothesis the prev_attn window of its parent row and its location features.
+// Wave w walks the 16-column tiles w, w + 4, .. of attn_dim: per tile the P
+// values, the W_loc fragment and w_attn are fetched once and kept in
+// registers across the hypotheses' e tiles (the fp32 MFMA contraction of
+// e_tile, + P + dech[n], tanh, the w_attn-weighted column sum, added into the
+// wave's LDS slot of (hypothesis, frame)).  Then each hypothesis's softmax
+// share, and the context partial (kGH x 32 probabilities) . (32 x E) on fp32
+// MFMA: enc is read once per workgroup, the waves split E.
+__global__ void __launch_bounds__(kST) beam_score_kernel(BeamArgs a) {
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
+  const int L = a.L, A = a.A, E = a.E, C = a.w_loc ? a.C : 0, nt = a.nt, ksz = a.ksz;
+  const int tile = blockIdx.x, b = blockIdx.y, g0 = blockIdx.z * kGH, l0 = tile * kLT;
+  const int gh = a.G - g0 < kGH ? a.G - g0 : kGH;
+  const int n0 = b * a.G + g0;
+  int len = a.enc_len[b];
+  len = len < 0 ? 0 : (len > L ? L : len);
+  const int KW = 2 * ksz + 1, Cq = cq_of(C), WW = kLT + 2 * ksz;
+  float* taps = lds;                             // [C][KW]
+  float* win = taps + C * KW;                    // [kGH][WW]
+  float* F = win + kGH * WW;                     // [kGH][kLT][Cq]
+  float* sred = lds + beam_stage_floats(C, ksz); // [kSW][kGH][kLT]
+  float* sc = sred + kSW * kGH * kLT;            // [kGH][kLT] scores, then p
+  for (int i = lane; i < kGH * kLT; i += 64) sred[w * kGH * kLT + i] = 0.f;
+  if (C) {
+    for (int i = tid; i < C * KW; i += kST) taps[i] = a.w_conv[i];
+    for (int i = tid; i < gh * WW; i += kST) {
+      const int gg = i / WW, x = i - gg * WW, f = l0 - ksz + x;
+      const float* prev = a.attn_prev + (long long)parent_row(a.parent, n0 + gg, a.G) * L;
+      win[i] = f >= 0 && f < L ? prev[f] : 0.f;
+    }
+    __syncthreads();
+    const int per = kLT * Cq;
+    for (int i = tid; i < kGH * per; i += kST) {
+      const int gg = i / per, rem = i - gg * per;
+      const int c = rem / kLT, l = rem - c * kLT;
+      float acc = 0.f;
+      if (gg < gh && c < C && l0 + l < L) {
+        const int lo = ksz - l0 - l > 0 ? ksz - l0 - l : 0;
+        const int hi = L - 1 - l0 - l + ksz < 2 * ksz ? L - 1 - l0 - l + ksz : 2 * ksz;
+        const float* tp = taps + c * KW;
+        const float* wn = win + gg * WW + l;
+        for (int j = lo; j <= hi; ++j) acc += tp[j] * wn[j];
+      }
+      F[(gg * kLT + l) * Cq + c] = acc;
+    }
+  }
+  __syncthreads();
+
+  const float* Prow = a.P + (long long)b * L * A;
+  const int nks = Cq >> 2;
+  float* mine = sred + w * kGH * kLT;
+  for (int ft = w; ft * 16 < A; ft += kSW) {
+    const int f = ft * 16 + (lane & 15);
+    const bool fin = f < A;
+    float bw[4 * kCT];
+#pragma unroll
+    for (int s = 0; s < 4 * kCT; ++s) {
+      const int k = 4 * s + g;
+      bw[s] = s < nks && fin && k < C ? a.w_loc[(long long)f * C + k] : 0.f;
+    }
+    float pv[kLMT][4];
+#pragma unroll
+    for (int m = 0; m < kLMT; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int l = l0 + m * 16 + 4 * g + r;
+        pv[m][r] = fin && l < len ? Prow[(long long)l * A + f] : 0.f;
+      }
+    const float wa = fin ? a.w_attn[f] : 0.f;
+    for (int gg = 0; gg < gh; ++gg) {
+      f32x4 e[kLMT];
+#pragma unroll
+      for (int m = 0; m < kLMT; ++m) e[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float* Fg = F + (gg * kLT + (lane & 15)) * Cq + g;
+#pragma unroll
+      for (int s = 0; s < 4 * kCT; ++s)
+        if (s < nks) {
+#pragma unroll
+          for (int m = 0; m < kLMT; ++m)
+            e[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(Fg[m * 16 * Cq + 4 * s], bw[s], e[m], 0, 0, 0);
+        }
+      const float dq = fin ? a.dech[(long long)(n0 + gg) * A + f] : 0.f;
+#pragma unroll
+      for (int m = 0; m < kLMT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = row16_sum_v(wa * tanhf(e[m][r] + pv[m][r] + dq));
+          if ((lane & 15) == 0) mine[gg * kLT + m * 16 + 4 * g + r] += v;
+        }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < kGH * kLT; i += kST) {
+    const int gg = i / kLT, l = i - gg * kLT;
+    float v = sred[i];
+#pragma unroll
+    for (int ww = 1; ww < kSW; ++ww) v += sred[ww * kGH * kLT + i];
+    v = gg < gh && l0 + l < len ? a.scaling * v : -INFINITY;
+    sc[i] = v;
+    if (gg < gh && l0 + l < L) a.scores[(long long)(n0 + gg) * L + l0 + l] = v;
+  }
+  __syncthreads();
+  // a hypothesis's tile maximum, p = exp(s - m) and their sum: one wave per hypothesis, both halves alike
+  for (int gg = w; gg < kGH; gg += kSW) {
+    const int l = lane & (kLT - 1);
+    const float s = sc[gg * kLT + l];
+    float mx = s;
+#pragma unroll
+    for (int o = kLT / 2; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float p = gg < gh && l0 + l < len ? expf(s - mx) : 0.f;
+    float sum = p;
+#pragma unroll
+    for (int o = kLT / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane < kLT) sc[gg * kLT + l] = p;
+    if (lane == 0 && gg < gh) {
+      float* o = a.ms + ((long long)(n0 + gg) * nt + tile) * 2;
+      o[0] = mx;
+      o[1] = sum;
+    }
+  }
+  __syncthreads();
+  // rows = hypotheses, K = the tile's frames, columns = 16 of E
+  float pa[kLT / 4];
+#pragma unroll
+  for (int s = 0; s < kLT / 4; ++s) pa[s] = sc[(lane & 15) * kLT + 4 * s + g];
+  const float* en = a.enc + (long long)b * L * E;
+  for (int et = w; et * 16 < E; et += kSW) {
+    const int e = et * 16 + (lane & 15);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < kLT / 4; ++s) {
+      const int l = l0 + 4 * s + g;
+      const float bv = e < E && l < len ? en[(long long)l * E + e] : 0.f;
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[s], bv, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int gg = 4 * g + r;
+      if (gg < gh && e < E) a.pctx[((long long)(n0 + gg) * nt + tile) * E + e] = acc[r];
+    }
+  }
+}
+
+// combine_kernel for row n, and in the same pass over the row: the first
+// index of its maximum, the attention-shift condition against the parent's
+// peak, the coverage cov_prev[parent] + attn (2 attn at the first step, as the
+// reference initialises with the step's attention and then adds it) and the
+// coverage penalty sum_l max(cov, 0.5) - 0.5 L
+__global__ void __launch_bounds__(kST) beam_combine_kernel(BeamArgs a) {
+  __shared__ float red16[16];
+  __shared__ float bestv[kSW];
+  __shared__ int besti[kSW];
+  const int tid = threadIdx.x, n = blockIdx.x, b = n / a.G;
+  const int L = a.L, E = a.E, nt = a.nt;
+  int len = a.enc_len[b];
+  len = len < 0 ? 0 : (len > L ? L : len);
+  const int p = parent_row(a.parent, n, a.G);
+  const float* ms = a.ms + (long long)n * nt * 2;
+  float M = ms[0];
+  for (int i = 1; i < nt; ++i) M = fmaxf(M, ms[2 * i]);
+  float S = 0.f;
+  for (int i = 0; i < nt; ++i)
+    if (ms[2 * i + 1] > 0.f) S += ms[2 * i + 1] * expf(ms[2 * i] - M);
+  const float inv = 1.f / S;
+  float bv = -INFINITY, part = 0.f;
+  int bi = 0x7fffffff;
+  for (int l = tid; l < L; l += kST) {
+    const float v = l < len ? expf(a.scores[(long long)n * L + l] - M) * inv : 0.f;
+    a.attn[(long long)n * L + l] = v;
+    const float cv = (a.first ? v : a.cov_prev[(long long)p * L + l]) + v;
+    a.cov[(long long)n * L + l] = cv;
+    part += fmaxf(cv, 0.5f);
+    if (v > bv) {
+      bv = v;
+      bi = l;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (ov > bv || (ov == bv && oi < bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  if ((tid & 63) == 0) {
+    bestv[tid >> 6] = bv;
+    besti[tid >> 6] = bi;
+  }
+  const float pen = block_sum(part, red16);   // its barriers publish bestv / besti
+  if (tid == 0) {
+    for (int ww = 1; ww < kSW; ++ww)
+      if (bestv[ww] > bv || (bestv[ww] == bv && besti[ww] < bi)) {
+        bv = bestv[ww];
+        bi = besti[ww];
+      }
+    const int pk = bi < L ? bi : 0, pp = a.peak_prev[p];
+    a.peak[n] = pk;
+    a.shift_ok[n] = pk <= pp + a.max_shift && pk > pp - a.max_shift;
+    a.pen[n] = pen - 0.5f * (float)L;
+  }
+  for (int e = tid; e < E; e += kST) {
+    float acc = 0.f;
+    for (int i = 0; i < nt; ++i)
+      if (ms[2 * i + 1] > 0.f) acc += a.pctx[((long long)n * nt + i) * E + e] * expf(ms[2 * i] - M);
+    a.ctx[(long long)n * E + e] = acc * inv;
+  }
+}
+
 inline bool bad_dims(int B, int T, int L, int H, int A, int O, int E) {
   if (B <= 0 || T <= 0 || L <= 0 || H <= 0 || A <= 0 || O <= 0 || E <= 0 || B > 65535) return true;
   const long long lim = 0x7fffffffLL;
@@ -757,4 +1104,66 @@ SBK_API int sbk_attdec_bwd(int bf16, const void* w_icT, const void* w_hhT, const
     if (int rc = launch(bf16 ? cell_bwd_kernel<bf16_t> : cell_bwd_kernel<float>, a, H, t, stream)) return rc;
   }
   return 0;
+}
+
+// hypotheses of one beam-score workgroup: its grid is (nt, B, ceil(G / this))
+SBK_API int sbk_attdec_beam_group() { return kGH; }
+
+// See include/sbk.h.
+SBK_API int sbk_attdec_beam_step(int bf16, const void* w_ic, const void* w_hh, const float* b_hh, const void* w_dec,
+                                 const float* b_q, const void* w_out, const float* b_out, const float* gx,
+                                 const int* token, const float* P, const float* enc, const int* enc_len,
+                                 const float* w_conv, const float* w_loc, const float* w_attn, float scaling,
+                                 const int* parent, const float* h_prev, const float* c_prev, const float* attn_prev,
+                                 const float* cov_prev, const int* peak_prev, int first, int max_shift, int V, int B,
+                                 int G, int L, int H, int A, int O, int E, int C, int ksz, float* h, float* c,
+                                 float* attn, float* cov, int* peak, int* shift_ok, float* pen, float* ctx,
+                                 float* dech, float* ws, void* stream) {
+  if (!w_ic || !w_hh || !w_dec || !w_out || !gx || !P || !enc || !enc_len || !w_attn || !parent || !h_prev ||
+      !c_prev || !cov_prev || !peak_prev || !h || !c || !attn || !cov || !peak || !shift_ok || !pen || !ctx || !dech ||
+      !ws)
+    return SBK_ERR_ARG;
+  if (G <= 0 || B <= 0 || (long long)B * G > 65535 || max_shift < 0 || max_shift > (1 << 30) || (token && V <= 0))
+    return SBK_ERR_ARG;
+  const int N = B * G;
+  if (bad_dims(N, 1, L, H, A, O, E)) return SBK_ERR_ARG;
+  if (w_loc ? (!w_conv || !attn_prev || C <= 0 || C > 16 * kCT || ksz < 0) : (w_conv != nullptr)) return SBK_ERR_ARG;
+  const int Ck = w_loc ? C : 0, nt = (L + kLT - 1) / kLT;
+  const size_t lds = sizeof(float) * ((size_t)beam_stage_floats(Ck, ksz) + (kSW + 1) * kGH * kLT);
+  if (lds > 160 * 1024 - 1024) return SBK_ERR_ARG;
+  if (lds > 64 * 1024)
+    if (hipError_t e = lds_optin((const void*)beam_score_kernel, lds)) return (int)e;
+  BeamArgs a;
+  a.w_ic = w_ic; a.w_hh = w_hh; a.b_hh = b_hh; a.gx = gx; a.token = token; a.P = P; a.enc = enc; a.enc_len = enc_len;
+  a.w_conv = w_conv; a.w_loc = w_loc; a.w_attn = w_attn; a.parent = parent;
+  a.h_prev = h_prev; a.c_prev = c_prev; a.attn_prev = attn_prev; a.cov_prev = cov_prev; a.peak_prev = peak_prev;
+  a.dech = dech; a.h = h; a.attn = attn; a.cov = cov; a.ctx = ctx; a.pen = pen; a.peak = peak; a.shift_ok = shift_ok;
+  a.scores = ws;
+  a.ms = a.scores + (size_t)N * L;
+  a.pctx = a.ms + (size_t)N * nt * 2;
+  a.scaling = scaling; a.first = first; a.max_shift = max_shift; a.V = V;
+  a.B = B; a.G = G; a.N = N; a.L = L; a.H = H; a.A = A; a.O = O; a.E = E; a.C = Ck; a.ksz = ksz; a.nt = nt;
+  a.vec_ic = vecw(w_ic, O, bf16);
+  a.vec_hh = vecw(w_hh, H, bf16);
+  a.vec_c = vecx(c_prev, O);
+  a.vec_h = vecx(h_prev, H);
+  // the query and the context projection are the sequence kernels at T = 1 over the N rows
+  FwdArgs f = {};
+  f.w_dec = w_dec; f.w_out = w_out; f.b_q = b_q; f.b_out = b_out;
+  f.hstate = h; f.cstate = c; f.ctx = ctx; f.dech = dech;
+  f.d = Dims{N, 1, L, H, A, O, E, Ck, ksz, nt};
+  f.vec_dec = vecw(w_dec, H, bf16);
+  f.vec_out = vecw(w_out, E, bf16);
+  f.vec_h = vecx(h, H);
+  f.vec_x = vecx(ctx, E);
+  const dim3 cgrid((H + kSlice - 1) / kSlice, (N + kRows - 1) / kRows);
+  hipLaunchKernelGGL(bf16 ? beam_cell_kernel<bf16_t> : beam_cell_kernel<float>, cgrid, dim3(kThreads), 0,
+                     (hipStream_t)stream, a);
+  SBK_CHECK_LAUNCH();
+  if (int rc = launch(bf16 ? query_kernel<bf16_t> : query_kernel<float>, f, A, 0, stream)) return rc;
+  hipLaunchKernelGGL(beam_score_kernel, dim3(nt, B, (G + kGH - 1) / kGH), dim3(kST), lds, (hipStream_t)stream, a);
+  SBK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(beam_combine_kernel, dim3(N), dim3(kST), 0, (hipStream_t)stream, a);
+  SBK_CHECK_LAUNCH();
+  return launch(bf16 ? cproj_kernel<bf16_t> : cproj_kernel<float>, f, O, 0, stream);
 }

@@ -1,6 +1,7 @@
 """Drop-ins for speechbrain.decoders.seq2seq (decoders/seq2seq.py) on MI355X:
-S2SBaseSearcher, S2SGreedySearcher, S2SBeamSearcher, S2STransformerBeamSearch
-and the helpers inflate_tensor, mask_by_condition,
+S2SBaseSearcher, S2SGreedySearcher, S2SBeamSearcher, S2STransformerBeamSearch,
+the RNN searchers S2SRNNGreedySearcher, S2SRNNBeamSearcher, S2SRNNBeamSearchLM,
+S2SRNNBeamSearchTransformerLM and the helpers inflate_tensor, mask_by_condition,
 batch_filter_seq2seq_output, filter_seq2seq_output.
 
 Same constructor arguments, defaults and return values as the reference
@@ -17,9 +18,23 @@ What runs where:
     bookkeeping, the final fill-up.  This is torch plumbing on device
     tensors; collecting the finished hypotheses reads the eos positions back
     once per step (the reference reads once per row).
-Not carried over, both RNN-searcher features that the reference itself
-mishandles for the transformer's 3-D attention map: using_max_attn_shift and
-coverage_penalty raise NotImplementedError.
+using_max_attn_shift and coverage_penalty are RNN-searcher features that the
+reference itself mishandles for the transformer's 3-D attention map: the RNN
+searchers take them (the reference's two branches of forward, through the
+hooks _mask_attn_shift / _permute_attn_peak / _coverage_penalty); the base
+class and S2STransformerBeamSearch raise NotImplementedError.
+RNN searchers: with S2SRNNBeamSearcher.USE_BEAM_STEP set (class or instance
+attribute; off by default) and `decoder` the
+package's AttentionalRNNDecoder on the device (not drawing dropout masks), a
+step is sbk_attdec_beam_step (csrc/attdec.hip, _attsearch.BeamState): the
+encoder states are never inflated (the _inflate_enc hook passes them through,
+mlp_enc runs once for the B utterances), the score kernel reads P and enc once
+per 16 hypotheses of an utterance, the embedding and the input half of W_ih
+are one (V, 3H) table row per token, and a beam permutation replaces the
+state's parent table and moves no data; the attention-shift condition and the
+coverage penalty come out of the step's combine kernel.  Otherwise the step is
+the reference's: dec.forward_step on inflated tensors and index_select on hs,
+c, prev_attn, the coverage and the peaks.
 Incremental decoding: with S2STransformerBeamSearch.USE_KV_CACHE set (class or
 instance attribute; off by default) and a decoder that
 TransformerASR.decode_step_supported() takes, a step runs decode_step — the
@@ -36,6 +51,7 @@ the LM runs on the whole prefix, as in the reference.
 """
 import torch
 
+from .. import _attsearch
 from .. import _kvdec  # registers the decode-step ops the cached search runs
 from ..lobes.models.transformer.TransformerLM import TransformerLM
 from .ctc import CTCPrefixScorer
@@ -95,6 +111,9 @@ class S2SGreedySearcher(S2SBaseSearcher):
 class S2SBeamSearcher(S2SBaseSearcher):
     """seq2seq.py:349-961."""
 
+    # using_max_attn_shift / coverage_penalty need a 2-D attention vector: only the RNN searchers set this
+    _RNN_SEARCHER = False
+
     def __init__(self, bos_index, eos_index, min_decode_ratio, max_decode_ratio, beam_size, topk=1,
                  return_log_probs=False, using_eos_threshold=True, eos_threshold=1.5, length_normalization=True,
                  length_rewarding=0, coverage_penalty=0.0, lm_weight=0.0, lm_modules=None, ctc_weight=0.0,
@@ -111,11 +130,11 @@ class S2SBeamSearcher(S2SBaseSearcher):
 
         if self.length_normalization and self.length_rewarding > 0:
             raise ValueError("length normalization is not compatible with length rewarding.")
-        if using_max_attn_shift:
+        if using_max_attn_shift and not self._RNN_SEARCHER:
             raise NotImplementedError(
                 "using_max_attn_shift is RNN-searcher-only: it takes the peak of a 2-D attention vector, and the "
                 "reference mishandles the transformer's 3-D attention map (seq2seq.py:500-525)")
-        if coverage_penalty > 0:
+        if coverage_penalty > 0 and not self._RNN_SEARCHER:
             raise NotImplementedError(
                 "coverage_penalty is RNN-searcher-only: the reference's transformer branch never updates the "
                 "coverage it penalises (seq2seq.py:833-835)")
@@ -198,8 +217,7 @@ class S2SBeamSearcher(S2SBaseSearcher):
                                          self.eos_index, self.ctc_window_size)
             ctc_memory = None
 
-        enc_states = inflate_tensor(enc_states, times=self.beam_size, dim=0)
-        enc_lens = inflate_tensor(enc_lens, times=self.beam_size, dim=0)
+        enc_states, enc_lens = self._inflate_enc(enc_states, enc_lens)
         inp_tokens = torch.full((batch_size * self.beam_size,), self.bos_index, device=device, dtype=torch.long)
         self.beam_offset = torch.arange(batch_size, device=device) * self.beam_size
 
@@ -215,6 +233,7 @@ class S2SBeamSearcher(S2SBaseSearcher):
         min_decode_steps = int(enc_states.shape[1] * self.min_decode_ratio)
         max_decode_steps = int(enc_states.shape[1] * self.max_decode_ratio)
         batch_index = torch.arange(batch_size, device=device).unsqueeze(1)
+        self.prev_attn_peak = torch.zeros(batch_size * self.beam_size, device=device)
 
         for t in range(max_decode_steps):
             if self._check_full_beams(hyps_and_scores, self.beam_size):
@@ -225,6 +244,8 @@ class S2SBeamSearcher(S2SBaseSearcher):
             log_probs_clone = log_probs.clone().reshape(batch_size, -1)
             vocab_size = log_probs.shape[-1]
 
+            if self.using_max_attn_shift:
+                log_probs = self._mask_attn_shift(log_probs, attn)
             if t < min_decode_steps:
                 log_probs[:, self.eos_index] = self.minus_inf
             if self.using_eos_threshold:
@@ -265,6 +286,13 @@ class S2SBeamSearcher(S2SBaseSearcher):
                 lm_memory = self.permute_lm_mem(lm_memory, index=predecessors)
             if self.ctc_weight > 0:
                 ctc_memory = ctc_scorer.permute_mem(ctc_memory, candidates)
+            if self.using_max_attn_shift:
+                self._permute_attn_peak(predecessors)
+            if self.coverage_penalty > 0:
+                # subtracted from scores only: sequence_scores carries no penalty (seq2seq.py:852)
+                penalty = self._coverage_penalty(attn, predecessors, t)
+                penalty = penalty / (t + 1) if self.length_normalization else penalty
+                scores = scores - penalty * self.coverage_penalty
 
             alived_seq = torch.cat([torch.index_select(alived_seq, dim=0, index=predecessors),
                                     inp_tokens.unsqueeze(1)], dim=-1)
@@ -288,6 +316,33 @@ class S2SBeamSearcher(S2SBaseSearcher):
         if self.return_log_probs:
             return predictions, topk_scores, log_probs
         return predictions, topk_scores
+
+    def _inflate_enc(self, enc_states, enc_lens):
+        """The encoder states as forward_step takes them: every utterance beam_size times."""
+        return (inflate_tensor(enc_states, times=self.beam_size, dim=0),
+                inflate_tensor(enc_lens, times=self.beam_size, dim=0))
+
+    def _mask_attn_shift(self, log_probs, attn):
+        """seq2seq.py:500-525, :734-740: rows whose attention peak moved max_attn_shift or more are blocked."""
+        _, attn_peak = torch.max(attn, dim=1)
+        cond = ((attn_peak <= self.prev_attn_peak + self.max_attn_shift)
+                * (attn_peak > self.prev_attn_peak - self.max_attn_shift)).unsqueeze(1)
+        self.prev_attn_peak = attn_peak
+        return mask_by_condition(log_probs, cond, fill_value=self.minus_inf)
+
+    def _permute_attn_peak(self, predecessors):
+        self.prev_attn_peak = torch.index_select(self.prev_attn_peak, dim=0, index=predecessors)
+
+    def _coverage_penalty(self, attn, predecessors, t):
+        """seq2seq.py:825-847 on a 2-D attn: the coverage is initialised with
+        the permuted attention and then updated with it, so it is twice the
+        attention after step 0."""
+        cur_attn = torch.index_select(attn, dim=0, index=predecessors)
+        if t == 0:
+            self.coverage = cur_attn
+        self.coverage = torch.index_select(self.coverage, dim=0, index=predecessors) + cur_attn
+        penalty = torch.max(self.coverage, self.coverage.clone().fill_(0.5)).sum(-1)
+        return penalty - self.coverage.size(-1) * 0.5
 
     def _add_lm_scores(self, log_probs, lm_log_probs):
         """LM fusion (seq2seq.py:756-760): what lm_forward_step returned, weighted, onto the step's scores."""
@@ -321,7 +376,50 @@ def _update_mem(inp_tokens, memory):
     return torch.cat([memory, inp_tokens.unsqueeze(1)], dim=-1)
 
 
-class S2STransformerBeamSearch(S2SBeamSearcher):
+class _TransformerLMSteps:
+    """LM fusion with a transformer LM (seq2seq.py:1234-1252, :1452-1470): the
+    whole prefix through the LM every step, or with USE_LM_KV_CACHE and a
+    TransformerLM that takes decode_step the newest token against the LM's
+    key/value cache.  _lm(): the LM module."""
+
+    USE_LM_KV_CACHE = False
+
+    def reset_lm_mem(self, batch_size, device):
+        return None
+
+    def _lm_kv_cache(self):
+        return (self.USE_LM_KV_CACHE and isinstance(self._lm(), TransformerLM)
+                and self._lm().decode_step_supported())
+
+    def permute_lm_mem(self, memory, index):
+        if self._lm_kv_cache():
+            return memory.permute(index)
+        return torch.index_select(memory, dim=0, index=index)
+
+    def lm_forward_step(self, inp_tokens, memory):
+        if self._lm_kv_cache():
+            # memory is the LM's decode state; what is returned are the raw
+            # logits of the newest position: _add_lm_scores takes them
+            if not next(self._lm().parameters()).is_cuda:
+                self._lm().to(inp_tokens.device)
+            if memory is None:
+                memory = self._lm().init_decode_state(inp_tokens.shape[0])
+            return self._lm().decode_step(inp_tokens, memory), memory
+        memory = _update_mem(inp_tokens, memory)
+        if not next(self._lm().parameters()).is_cuda:
+            self._lm().to(inp_tokens.device)
+        logits = self._lm()(memory)
+        log_probs = self.softmax(logits / self.temperature_lm)
+        return log_probs[:, -1, :], memory
+
+    def _add_lm_scores(self, log_probs, lm_log_probs):
+        if self._lm_kv_cache():
+            # lm_log_probs are the logits: temperature, log-softmax, weight and add in one kernel
+            return _kvdec.log_softmax_fuse(lm_log_probs, log_probs, 1.0 / self.temperature_lm, self.lm_weight)
+        return super()._add_lm_scores(log_probs, lm_log_probs)
+
+
+class S2STransformerBeamSearch(_TransformerLMSteps, S2SBeamSearcher):
     """seq2seq.py:1334-1398.  modules = [TransformerASR, seq_lin, ctc_lin]."""
 
     # incremental decoding through TransformerASR.decode_step; the constructor
@@ -342,23 +440,14 @@ class S2STransformerBeamSearch(S2SBeamSearcher):
     def reset_mem(self, batch_size, device):
         return None
 
-    def reset_lm_mem(self, batch_size, device):
-        return None
+    def _lm(self):
+        return self.lm_modules
 
     def _kv_cache(self):
         return self.USE_KV_CACHE and self.model.decode_step_supported()
 
     def permute_mem(self, memory, index):
         if self._kv_cache():
-            return memory.permute(index)
-        return torch.index_select(memory, dim=0, index=index)
-
-    def _lm_kv_cache(self):
-        return (self.USE_LM_KV_CACHE and isinstance(self.lm_modules, TransformerLM)
-                and self.lm_modules.decode_step_supported())
-
-    def permute_lm_mem(self, memory, index):
-        if self._lm_kv_cache():
             return memory.permute(index)
         return torch.index_select(memory, dim=0, index=index)
 
@@ -376,27 +465,140 @@ class S2STransformerBeamSearch(S2SBeamSearcher):
         prob_dist = self.softmax(self.fc(pred) / self.temperature)
         return prob_dist[:, -1, :], memory, attn
 
-    def lm_forward_step(self, inp_tokens, memory):
-        if self._lm_kv_cache():
-            # memory is the LM's decode state; what is returned are the raw
-            # logits of the newest position: _add_lm_scores takes them
-            if not next(self.lm_modules.parameters()).is_cuda:
-                self.lm_modules.to(inp_tokens.device)
-            if memory is None:
-                memory = self.lm_modules.init_decode_state(inp_tokens.shape[0])
-            return self.lm_modules.decode_step(inp_tokens, memory), memory
-        memory = _update_mem(inp_tokens, memory)
-        if not next(self.lm_modules.parameters()).is_cuda:
-            self.lm_modules.to(inp_tokens.device)
-        logits = self.lm_modules(memory)
-        log_probs = self.softmax(logits / self.temperature_lm)
-        return log_probs[:, -1, :], memory
 
-    def _add_lm_scores(self, log_probs, lm_log_probs):
-        if self._lm_kv_cache():
-            # lm_log_probs are the logits: temperature, log-softmax, weight and add in one kernel
-            return _kvdec.log_softmax_fuse(lm_log_probs, log_probs, 1.0 / self.temperature_lm, self.lm_weight)
-        return super()._add_lm_scores(log_probs, lm_log_probs)
+class S2SRNNGreedySearcher(S2SGreedySearcher):
+    """seq2seq.py:284-346: greedy decoding with an AttentionalRNNDecoder."""
+
+    def __init__(self, embedding, decoder, linear, **kwargs):
+        super().__init__(**kwargs)
+        self.emb = embedding
+        self.dec = decoder
+        self.fc = linear
+        self.softmax = torch.nn.LogSoftmax(dim=-1)
+
+    def reset_mem(self, batch_size, device):
+        self.dec.attn.reset()
+        return None, torch.zeros(batch_size, self.dec.attn_dim, device=device)
+
+    def forward_step(self, inp_tokens, memory, enc_states, enc_lens):
+        hs, c = memory
+        dec_out, hs, c, w = self.dec.forward_step(self.emb(inp_tokens), hs, c, enc_states, enc_lens)
+        return self.softmax(self.fc(dec_out)), (hs, c), w
+
+
+class S2SRNNBeamSearcher(S2SBeamSearcher):
+    """seq2seq.py:964-1069: beam search with an AttentionalRNNDecoder."""
+
+    _RNN_SEARCHER = True
+    # the beam-grouped step (sbk_attdec_beam_step); the constructor is the
+    # reference's, so this is an attribute (as S2STransformerBeamSearch.USE_KV_CACHE).
+    # Off by default: at beam 80 it needs a ninth of the memory but is not
+    # faster than the reference's step (scripts/rnn_search_ab.py, DESIGN §3l)
+    USE_BEAM_STEP = False
+
+    def __init__(self, embedding, decoder, linear, ctc_linear=None, temperature=1.0, **kwargs):
+        super().__init__(**kwargs)
+        self.emb = embedding
+        self.dec = decoder
+        self.fc = linear
+        self.ctc_fc = ctc_linear
+        if self.ctc_weight > 0.0 and self.ctc_fc is None:
+            raise ValueError("To perform joint ATT/CTC decoding, ctc_fc is required.")
+        self.softmax = torch.nn.LogSoftmax(dim=-1)
+        self.temperature = temperature
+
+    def _beam_step(self):
+        from ..nnet.RNN import AttentionalRNNDecoder
+        dec = self.dec
+        return (self.USE_BEAM_STEP and isinstance(dec, AttentionalRNNDecoder) and dec.proj.weight.is_cuda
+                and not (dec.training and dec.drop.p > 0))
+
+    def reset_mem(self, batch_size, device):
+        self.dec.attn.reset()
+        if self._beam_step():
+            return None     # the beam state: built by the first step, which sees the encoder states
+        return None, torch.zeros(batch_size, self.dec.attn_dim, device=device)
+
+    def _inflate_enc(self, enc_states, enc_lens):
+        if self._beam_step():
+            return enc_states, enc_lens
+        return super()._inflate_enc(enc_states, enc_lens)
+
+    def forward_step(self, inp_tokens, memory, enc_states, enc_lens):
+        if self._beam_step():
+            if memory is None:
+                memory = _attsearch.BeamState(self.dec, self.emb, enc_states, enc_lens, self.beam_size,
+                                              self.max_attn_shift)
+            self._state = memory
+            dec_out, w = memory.step(inp_tokens)
+            return self.softmax(self.fc(dec_out) / self.temperature), memory, w
+        hs, c = memory
+        dec_out, hs, c, w = self.dec.forward_step(self.emb(inp_tokens), hs, c, enc_states, enc_lens)
+        return self.softmax(self.fc(dec_out) / self.temperature), (hs, c), w
+
+    def permute_mem(self, memory, index):
+        if self._beam_step():
+            return memory.permute(index)
+        hs, c = memory
+        hs = torch.index_select(hs, dim=1, index=index)
+        c = torch.index_select(c, dim=0, index=index)
+        if self.dec.attn_type == "location":
+            self.dec.attn.prev_attn = torch.index_select(self.dec.attn.prev_attn, dim=0, index=index)
+        return hs, c
+
+    # with the grouped step the combine kernel has already compared row n's
+    # peak with its parent's and summed its coverage; pen is by row of the
+    # step, so the permuted rows gather it
+    def _mask_attn_shift(self, log_probs, attn):
+        if self._beam_step():
+            return mask_by_condition(log_probs, self._state.shift_ok.bool().unsqueeze(1), fill_value=self.minus_inf)
+        return super()._mask_attn_shift(log_probs, attn)
+
+    def _permute_attn_peak(self, predecessors):
+        if not self._beam_step():
+            super()._permute_attn_peak(predecessors)
+
+    def _coverage_penalty(self, attn, predecessors, t):
+        if self._beam_step():
+            return torch.index_select(self._state.pen, dim=0, index=predecessors)
+        return super()._coverage_penalty(attn, predecessors, t)
+
+
+class S2SRNNBeamSearchLM(S2SRNNBeamSearcher):
+    """seq2seq.py:1072-1165.  language_model: (tokens, hx=memory) -> (logits,
+    memory), the memory a tensor or a tuple of tensors with the rows on dim 1."""
+
+    def __init__(self, embedding, decoder, linear, language_model, temperature_lm=1.0, **kwargs):
+        super().__init__(embedding, decoder, linear, **kwargs)
+        self.lm = language_model
+        self.lm.eval()
+        self.log_softmax = torch.nn.LogSoftmax(dim=-1)
+        self.temperature_lm = temperature_lm
+
+    def lm_forward_step(self, inp_tokens, memory):
+        logits, hs = self.lm(inp_tokens, hx=memory)
+        return self.log_softmax(logits / self.temperature_lm), hs
+
+    def permute_lm_mem(self, memory, index):
+        if isinstance(memory, tuple):
+            return tuple(torch.index_select(m, dim=1, index=index) for m in memory)
+        return torch.index_select(memory, dim=1, index=index)
+
+    def reset_lm_mem(self, batch_size, device):
+        return None
+
+
+class S2SRNNBeamSearchTransformerLM(_TransformerLMSteps, S2SRNNBeamSearcher):
+    """seq2seq.py:1168-1252; USE_LM_KV_CACHE as S2STransformerBeamSearch."""
+
+    def __init__(self, embedding, decoder, linear, language_model, temperature_lm=1.0, **kwargs):
+        super().__init__(embedding, decoder, linear, **kwargs)
+        self.lm = language_model
+        self.lm.eval()
+        self.temperature_lm = temperature_lm
+
+    def _lm(self):
+        return self.lm
 
 
 def batch_filter_seq2seq_output(prediction, eos_id=-1):
