@@ -1153,6 +1153,43 @@ int sbk_drop_chunks(const float* x, int B, int T, int C, const int* segs, int S,
 int sbk_tdaug(const float* x, int B, int T, const int* first, const float* w, int L, int M, int W, int T_out,
               const float* taps, const int* segs, int S, float* y, void* stream);
 
+/* ------------------------------------------------------------ csrc/convln.hip
+ * One layer of the CRDNN CNN_Block (lobes/models/CRDNN.py:197-276): Conv2d
+ * 3x3, stride 1, "same" reflect padding, bias (null: none) -> LayerNorm over
+ * (F, Co) with affine gamma / beta (F, Co) -> LeakyReLU(slope) -> max-pool
+ * over frequency, kernel = stride = pool, floor mode (1: none) -> times
+ * scale (B, F / pool) (null: none; the lobe's Dropout2d mask), in one launch
+ * as an implicit GEMM: x (B, T, F, Ci) -> y (B, T, F / pool, Co), both in the
+ * compute dtype (bf16 = 1 / 0: bf16 or fp32 storage and MFMA; fp32
+ * accumulation and statistics).  img = sbk_conv3x3_ln_image of the weight
+ * w (Co, Ci, kF, kT) fp32: sbk_conv3x3_ln_image_elems(bf16, Ci, Co) elements
+ * of the compute dtype, 0 for an unsupported pair.  For training c (B*T*F,
+ * Co), the conv output rounded to the compute dtype, and mean / rstd (B*T)
+ * receive what the backward needs (all three or none).
+ * Supported: T >= 2, 2 <= F <= 160, Co a multiple of 16 up to 256,
+ * F * Co <= 16384, any Ci whose slab fits the LDS plan —
+ * sbk_conv3x3_ln_frames returns the frames a workgroup owns, 0 when the
+ * shape is unsupported; sbk_conv3x3_ln then returns the argument error
+ * before anything is written. */
+int sbk_conv3x3_ln_frames(int bf16, int F, int Ci, int Co);
+long long sbk_conv3x3_ln_image_elems(int bf16, int Ci, int Co);
+int sbk_conv3x3_ln_image(int bf16, const float* w, int Ci, int Co, void* img, void* stream);
+int sbk_conv3x3_ln(int bf16, const void* x, int B, int T, int F, int Ci, int Co, const void* img, const float* bias,
+                   const float* gamma, const float* beta, float eps, float slope, int pool, const float* scale, void* y,
+                   void* c, float* mean, float* rstd, void* stream);
+
+/* Its backward up to the convolution: from dy (B, T, F / pool, Co), c, mean,
+ * rstd, the affine and the scale it recomputes the normalised values and
+ * activations, routes dy to the first maximum of each pool window, applies
+ * LeakyReLU' and the LayerNorm backward and writes dc (B*T*F, Co); dy, c, dc
+ * in the compute dtype.  part (sbk_conv3x3_ln_bwd_blocks(B*T), 2, F*Co)
+ * receives per-workgroup [dgamma | dbeta] partials (reduce with sbk_colsum;
+ * no atomics: runs are bit-identical).  F * Co <= 16384. */
+int sbk_conv3x3_ln_bwd_blocks(int rows);
+int sbk_conv3x3_ln_bwd(int bf16, const void* dy, const void* c, const float* mean, const float* rstd,
+                       const float* gamma, const float* beta, const float* scale, int B, int T, int F, int Co, int pool,
+                       float slope, void* dc, float* part, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

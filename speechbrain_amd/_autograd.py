@@ -554,6 +554,116 @@ class ConvBlockFn(Function):
         return dx, dw, db, dlw, dlb, None, None, None, None, None
 
 
+def cnn_block_frames(dtype, F, Ci, Co):
+    """Frames a workgroup of the fused CNN_Block kernel owns for this shape;
+    0: the shape is outside its supported set (ConvBlockFn takes it)."""
+    return int(lib().sbk_conv3x3_ln_frames(int(dtype == _bf16), F, Ci, Co))
+
+
+def _cnn_image(w, dtype):
+    """The 3x3 weight (Co, Ci, kF, kT) as csrc/convln.hip streams it."""
+    Co, Ci = w.shape[:2]
+    L = lib()
+    n = int(L.sbk_conv3x3_ln_image_elems(int(dtype == _bf16), Ci, Co))
+    img = torch.empty(n, device=w.device, dtype=dtype)
+    check(L.sbk_conv3x3_ln_image(int(dtype == _bf16), ptr(_cont(w.detach().float())), Ci, Co, ptr(img), stream_of(w)),
+          "sbk_conv3x3_ln_image")
+    return img
+
+
+class CnnBlockFn(Function):
+    """One layer of the CRDNN CNN_Block (lobes/models/CRDNN.py:197-276) in one
+    launch of csrc/convln.hip: Conv2d 3x3 stride 1 "same" reflect -> LayerNorm
+    over (freq, chan) -> LeakyReLU -> max-pool over frequency (kernel = stride
+    = pool, floor mode; 1: none) -> times scale (B, F // pool) or None (the
+    Dropout2d mask).  x (B, T, F, Ci) and y (B, T, F // pool, Co) in the
+    compute dtype `dtype`; img the weight image (cached by the caller per
+    weight version).  Saved for the backward: x, the conv output c in the
+    compute dtype and the per-frame mean / rstd — no col matrix.  Backward:
+    sbk_conv3x3_ln_bwd gives dc and the dgamma / dbeta partials; the weight
+    and input gradients run on the existing GEMMs over a transient im2col."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, ln_w, ln_b, eps, slope, pool, scale, dtype, img):
+        x = _as(x, dtype)
+        B, T, F, Ci = x.shape
+        Co = w.shape[0]
+        L = lib()
+        train = any(ctx.needs_input_grad)
+        y = torch.empty(B, T, F // pool, Co, device=x.device, dtype=dtype)
+        c = mean = rstd = None
+        if train:
+            c = torch.empty(B * T * F, Co, device=x.device, dtype=dtype)
+            mean = torch.empty(B * T, device=x.device, dtype=_f32)
+            rstd = torch.empty(B * T, device=x.device, dtype=_f32)
+        check(L.sbk_conv3x3_ln(_bf(x), ptr(x), B, T, F, Ci, Co, ptr(img), ptr(None if bias is None else bias.detach()),
+                               ptr(ln_w.detach()), ptr(ln_b.detach()), float(eps), float(slope), pool, ptr(scale),
+                               ptr(y), ptr(c), ptr(mean), ptr(rstd), stream_of(x)), "sbk_conv3x3_ln")
+        ctx.save_for_backward(x, w, c, mean, rstd, ln_w, ln_b, scale)
+        ctx.cfg = (slope, pool, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, c, mean, rstd, ln_w, ln_b, scale = ctx.saved_tensors
+        slope, pool, has_bias = ctx.cfg
+        B, T, F, Ci = x.shape
+        Co = w.shape[0]
+        D = F * Co
+        dtype = x.dtype
+        L = lib()
+        s = stream_of(x)
+        dy = _as(dy, dtype)
+        nblk = int(L.sbk_conv3x3_ln_bwd_blocks(B * T))
+        part = torch.empty(nblk * 2 * D, device=x.device, dtype=_f32)
+        dc = torch.empty(B * T * F, Co, device=x.device, dtype=dtype)
+        check(L.sbk_conv3x3_ln_bwd(_bf(x), ptr(dy), ptr(c), ptr(mean), ptr(rstd), ptr(ln_w.detach()),
+                                   ptr(ln_b.detach()), ptr(scale), B, T, F, Co, pool, float(slope), ptr(dc), ptr(part),
+                                   s), "sbk_conv3x3_ln_bwd")
+        gb = colsum(part, nblk, 2 * D)
+        dlw, dlb = gb[:D].view_as(ln_w), gb[D:].view_as(ln_w)
+        # wgrad / dgrad on the existing GEMMs: col lives for this backward only
+        vec = 8 if dtype == _bf16 else 4
+        K = 9 * Ci
+        ldcol = -(-K // vec) * vec
+        dw = dx = None
+        if ctx.needs_input_grad[1]:
+            col = torch.empty(B * T * F, ldcol, device=x.device, dtype=dtype)
+            check(L.sbk_im2col(ptr(x), _bf(x), B, T, F, Ci, 3, 3, 1, 1, 1, 1, ldcol, ptr(col), _bf(col), s),
+                  "sbk_im2col")
+            dw = wgrad(dc, col)[:, :K].reshape(Co, 3, 3, Ci).permute(0, 3, 2, 1).reshape(w.shape)
+            del col
+        db = rowsum(dc) if has_bias and ctx.needs_input_grad[2] else None
+        if ctx.needs_input_grad[0]:
+            wp = torch.zeros(Co, ldcol, device=x.device, dtype=_f32)
+            wp[:, :K] = w.detach().permute(0, 3, 2, 1).reshape(Co, K)
+            dcol = dgrad(dc, _as(wp, dtype))
+            dx = torch.empty(B, T, F, Ci, device=x.device, dtype=dtype)
+            check(L.sbk_col2im(ptr(dcol), _bf(dcol), B, T, F, Ci, 3, 3, 1, 1, 1, 1, ldcol, ptr(dx), _bf(dx), s),
+                  "sbk_col2im")
+        return dx, dw, db, dlw, dlb, None, None, None, None, None, None
+
+
+def cnn_block(x, w, bias, ln_w, ln_b, eps, slope, pool, scale, dtype, cache, key, fused=True):
+    """conv 3x3 + LayerNorm + LeakyReLU [+ frequency max-pool] [* scale] of
+    x (B, T, F, Ci) -> (B, T, F // pool, Co) in the compute dtype: CnnBlockFn
+    where the kernel supports the shape (and `fused`), else ConvBlockFn
+    followed by torch's pool and the multiply."""
+    B, T, F, Ci = x.shape
+    Co = w.shape[0]
+    if (fused and tuple(w.shape[2:]) == (3, 3) and T >= 2 and 1 <= pool <= F
+            and cnn_block_frames(dtype, F, Ci, Co) > 0):
+        img = cache.get((key, dtype), [w], lambda: _cnn_image(w, dtype))
+        return CnnBlockFn.apply(to_dtype(x, dtype), w, bias, ln_w, ln_b, eps, slope, pool, scale, dtype, img)
+    xin = x if (x.dtype == dtype or Ci == 1) else to_dtype(x, dtype)
+    y = ConvBlockFn.apply(xin, w, bias, ln_w, ln_b, eps, slope, dtype, dtype, (w.shape[3], w.shape[2], 1, 1))
+    if pool > 1:
+        y = torch.nn.functional.max_pool2d(y.permute(0, 3, 1, 2), (1, pool)).permute(0, 2, 3, 1)
+    if scale is not None:
+        y = y * scale.to(y.dtype)[:, None, :, None]
+    return y
+
+
 class Conv2dXFn(Function):
     """The standalone Conv2d's general geometry (CNN.py:616-700): dilation,
     per-side padding and the F.pad modes, as sbk_im2col_x + the MFMA GEMM.

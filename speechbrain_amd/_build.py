@@ -26,8 +26,10 @@ CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-a
 
 
 # per-source additions: attdec.hip is compiled without the packed fp32 VALU
-# forms (v_pk_add/mul/fma_f32), so its epilogues are scalar fp32 throughout
-EXTRA = {"attdec.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# forms (v_pk_add/mul/fma_f32), so its epilogues are scalar fp32 throughout;
+# convln.hip likewise
+_NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA = {"attdec.hip": _NO_PK, "convln.hip": _NO_PK}
 
 
 def _flags_changed():

@@ -216,8 +216,15 @@ SIGNATURES = {
     "sbk_dropout_add": [_vp, _i, _vp, _ll, _i, _vp, _f, _f, ctypes.c_ulonglong, _vp, _i, _vp],
     "sbk_joint_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "sbk_joint_bwd_workspace_floats": [_i, _i, _i, _i],
+    # convln.hip (CRDNN CNN_Block layer: 3x3 stride-1 conv + LayerNorm + LeakyReLU + pool, and its backward epilogue)
+    "sbk_conv3x3_ln_frames": [_i, _i, _i, _i],
+    "sbk_conv3x3_ln_image_elems": [_i, _i, _i],
+    "sbk_conv3x3_ln_image": [_i, _vp, _i, _i, _vp, _vp],
+    "sbk_conv3x3_ln": [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sbk_conv3x3_ln_bwd_blocks": [_i],
+    "sbk_conv3x3_ln_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp],
 }
-RESTYPES = {"sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_conv_image_elems": ctypes.c_longlong, "sbk_wo_image_elems": ctypes.c_longlong, "sbk_dw_image_elems": ctypes.c_longlong, "sbk_src_image_elems": ctypes.c_longlong,"sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong, "sbk_ctc_workspace_floats": ctypes.c_longlong}
+RESTYPES = {"sbk_conv3x3_ln_image_elems": ctypes.c_longlong, "sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_conv_image_elems": ctypes.c_longlong, "sbk_wo_image_elems": ctypes.c_longlong, "sbk_dw_image_elems": ctypes.c_longlong, "sbk_src_image_elems": ctypes.c_longlong,"sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong, "sbk_ctc_workspace_floats": ctypes.c_longlong}
 
 _lib = None
 _load_error = None
