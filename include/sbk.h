@@ -1190,6 +1190,62 @@ int sbk_conv3x3_ln_bwd(int bf16, const void* dy, const void* c, const float* mea
                        const float* gamma, const float* beta, const float* scale, int B, int T, int F, int Co, int pool,
                        float slope, void* dc, float* part, void* stream);
 
+/* ------------------------------------------------------------- csrc/ecapa.hip
+ * The eval forward of the ECAPA-TDNN lobe, time major: activations (N, L, C)
+ * in the compute dtype (bf16 = 1 / 0), C contiguous, rows ld* elements apart
+ * (a channel range of a wider buffer: pass the pointer of its first channel).
+ *
+ * sbk_tdnn: out[n, t, co] = tanh?(scale[co] * act(sum_j sum_ci wp[j, co, ci] *
+ * u[n, refl(t + (j - (k-1)/2) d), ci] + bias) + shift[co]), u = x (+ add),
+ * refl the reflection over the L frames, act LeakyReLU(slope) (0: ReLU,
+ * 1: none).  wp (k, Co, cipad) in the compute dtype, 16-byte aligned, cipad
+ * = Ci rounded up to 32, zero past Ci.  bias (Co) or, bias_per_utt, (N, Co);
+ * bias, scale, shift, add, valid, part may be null.  part (N, tiles, Co),
+ * tiles = ceil(L / sbk_tdnn_tile()): per frame tile the column sums of out
+ * over the frames t < valid[n] (all L without valid), fixed order, no
+ * atomics.  k odd <= 5, (k - 1) d <= 32, (k - 1) d / 2 < L, Co a multiple
+ * of 8.  Anything else returns the argument error with nothing written. */
+int sbk_tdnn_tile(void);
+int sbk_tdnn(int bf16, const void* x, long long ldx, const void* add, long long ldadd, int N, int L, int Ci, int Co,
+             int k, int d, const void* wp, int cipad, const float* bias, int bias_per_utt, float slope,
+             const float* scale, const float* shift, int tanh_, void* out, long long ldo, const int* valid, float* part,
+             void* stream);
+
+/* The whole Res2Net block in one launch: chunk width w = C / scale; chunk 0
+ * of x (N, L, scale w) is copied to out; for i = 1 .. scale - 1, u_i = x_i
+ * (+ y_{i-1}), y_i = aff_i(relu(conv_i(u_i) + bias_i)) to channels [i w,
+ * (i + 1) w) of out, every step reflect-padding its own input over the L
+ * frames.  wp (scale - 1, k, w, w rounded up to 32) in the compute dtype, the
+ * sbk_tdnn layout per step; bias (null: none), aff_scale, aff_shift (scale -
+ * 1, w) fp32.  x and out distinct.  sbk_res2net_supported: w a multiple of 8
+ * up to 128, k odd <= 5, (scale - 1) d (k - 1) <= 64 (the halo of a 64-frame
+ * tile inside 128 LDS rows); anything else is the argument error. */
+int sbk_res2net_supported(int w, int scale, int k, int d);
+int sbk_res2net(int bf16, const void* x, long long ldx, int N, int L, int w, int scale, int k, int d, const void* wp,
+                const float* bias, const float* aff_scale, const float* aff_shift, void* out, long long ldo,
+                void* stream);
+
+/* Squeeze-excitation from sbk_tdnn's partials: m = sum_tiles part / valid[n]
+ * (L without valid), s (N, C) = sigmoid(w2 relu(w1 m + b1) + b2), w1 (S, C),
+ * w2 (C, S) fp32; then out = s[n, c] * x + res, x (N*L, C) contiguous, res
+ * (null: none) and out through row strides. */
+int sbk_se_gate(const float* part, int tiles, const int* valid, int N, int L, int C, int S, const float* w1,
+                const float* b1, const float* w2, const float* b2, float* s, void* stream);
+int sbk_se_apply(int bf16, const void* x, const float* s, const void* res, long long ldr, void* out, long long ldo,
+                 int N, int L, int C, void* stream);
+
+/* Attentive statistics pooling.  sbk_asp_stats: mean and sqrt(max(var,
+ * 1e-12)) of x over the frames t < valid[n], (N, C) fp32 each.  sbk_asp_pool:
+ * logits[t, c] = h[n, t, :] . wc[c, :] + bc[c] over the same frames, h (N, L,
+ * A) and wc (C, A) in the compute dtype, 16-byte aligned; softmax over t per
+ * channel (online, fp32) and out (N, 2 C) = [sum_t p x | sqrt(max(sum_t p
+ * (x - mean)^2, 1e-12))], accumulated about the pivot mu (N, C) (the mean of
+ * sbk_asp_stats).  A a multiple of 8, C of 16. */
+int sbk_asp_stats(int bf16, const void* x, long long ldx, const int* valid, int N, int L, int C, float* mean, float* sd,
+                  void* stream);
+int sbk_asp_pool(int bf16, const void* h, const void* wc, const float* bc, const void* x, long long ldx,
+                 const float* mu, const int* valid, int N, int L, int A, int C, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,16 @@ SIGNATURES = {
     "sbk_conv3x3_ln": [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "sbk_conv3x3_ln_bwd_blocks": [_i],
     "sbk_conv3x3_ln_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp],
+    # ecapa.hip (ECAPA-TDNN eval forward: TDNN layer, squeeze-excitation, attentive statistics pooling)
+    "sbk_tdnn_tile": [],
+    "sbk_tdnn": [_i, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _i, _vp, _ll, _vp,
+                 _vp, _vp],
+    "sbk_res2net_supported": [_i, _i, _i, _i],
+    "sbk_res2net": [_i, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp],
+    "sbk_se_gate": [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sbk_se_apply": [_i, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _vp],
+    "sbk_asp_stats": [_i, _vp, _ll, _vp, _i, _i, _i, _vp, _vp, _vp],
+    "sbk_asp_pool": [_i, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
 }
 RESTYPES = {"sbk_conv3x3_ln_image_elems": ctypes.c_longlong, "sbk_relpos_attention_lds": ctypes.c_longlong, "sbk_mx_gemm_ws_floats": ctypes.c_longlong, "sbk_ffn_image_elems": ctypes.c_longlong, "sbk_conv_image_elems": ctypes.c_longlong, "sbk_wo_image_elems": ctypes.c_longlong, "sbk_dw_image_elems": ctypes.c_longlong, "sbk_src_image_elems": ctypes.c_longlong,"sbk_joint_bwd_workspace_floats": ctypes.c_longlong, "sbk_rnnt_workspace_floats": ctypes.c_longlong, "sbk_ctc_workspace_floats": ctypes.c_longlong}
 

@@ -7,14 +7,21 @@ im2col kernels + the MFMA GEMM, differentiable: "same" reflect with
 dilation 1 on the ConvBlock path (_autograd.ConvBlockFn without norm and
 activation); any other stride / dilation / groups / padding ("same" with
 every padding_mode, "valid", "causal", get_padding_elem :1459-1481) and
-skip_transpose on sbk_im2col_x / sbk_col2im_x (_autograd.Conv2dXFn)."""
+skip_transpose on sbk_im2col_x / sbk_col2im_x (_autograd.Conv2dXFn).
+
+Conv1d (CNN.py:309-501; conv.weight / conv.bias) is a thin wrapper over
+torch's device conv, as BatchNorm1d and Pooling1d are: the differentiable
+path of the TDNN layers, whose eval forward runs on csrc/ecapa.hip
+(lobes.models.ECAPA_TDNN)."""
 import math
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _autograd as A
 from .. import _enc
+from .._lib import require_device
 
 
 def get_padding_elem(L_in: int, stride: int, kernel_size: int, dilation: int):
@@ -23,6 +30,79 @@ def get_padding_elem(L_in: int, stride: int, kernel_size: int, dilation: int):
         return [math.floor(kernel_size / 2), math.floor(kernel_size / 2)]
     L_out = math.floor((L_in - dilation * (kernel_size - 1) - 1) / stride) + 1
     return [math.floor((L_in - L_out) / 2), math.floor((L_in - L_out) / 2)]
+
+
+class Conv1d(nn.Module):
+    def __init__(self, out_channels, kernel_size, input_shape=None, in_channels=None, stride=1, dilation=1,
+                 padding="same", groups=1, bias=True, padding_mode="reflect", skip_transpose=False, weight_norm=False,
+                 conv_init=None):
+        super().__init__()
+        self.kernel_size = kernel_size
+        self.stride = stride
+        self.dilation = dilation
+        self.padding = padding
+        self.padding_mode = padding_mode
+        self.unsqueeze = False
+        self.skip_transpose = skip_transpose
+        if input_shape is None and in_channels is None:
+            raise ValueError("Must provide one of input_shape or in_channels")
+        if in_channels is None:
+            in_channels = self._check_input_shape(input_shape)
+        self.in_channels = in_channels
+        self.conv = nn.Conv1d(in_channels, out_channels, self.kernel_size, stride=self.stride,
+                              dilation=self.dilation, padding=0, groups=groups, bias=bias)
+        if conv_init == "kaiming":
+            nn.init.kaiming_normal_(self.conv.weight)
+        self.weight_norm = bool(weight_norm)
+        if weight_norm:
+            self.conv = nn.utils.weight_norm(self.conv)
+        self.groups = groups
+
+    def _check_input_shape(self, shape):
+        if len(shape) == 2:
+            self.unsqueeze = True
+            in_channels = 1
+        elif self.skip_transpose:
+            in_channels = shape[1]
+        elif len(shape) == 3:
+            in_channels = shape[2]
+        else:
+            raise ValueError("conv1d expects 2d, 3d inputs. Got " + str(len(shape)))
+        if not self.padding == "valid" and self.kernel_size % 2 == 0:
+            raise ValueError("The field kernel size must be an odd number. Got %s." % (self.kernel_size))
+        return in_channels
+
+    def same_pad(self):
+        """Frames "same" pads per side (_manage_padding :446-473, whose L_in is the channel count)."""
+        return get_padding_elem(self.in_channels, self.stride, self.kernel_size, self.dilation)[0]
+
+    def forward(self, x):
+        """CNN.py:404-444: x (B, T, C) — (B, C, T) with skip_transpose, (B, T) for a 2-D input_shape."""
+        require_device(x)
+        if not self.skip_transpose:
+            x = x.transpose(1, -1)
+        if self.unsqueeze:
+            x = x.unsqueeze(1)
+        if self.padding == "same":
+            pad = self.same_pad()
+            mode = "constant" if self.padding_mode == "zeros" else self.padding_mode
+            if mode == "reflect" and pad >= x.shape[-1]:
+                raise ValueError("Conv1d: reflect padding needs more frames than the padding")
+            x = F.pad(x, (pad, pad), mode=mode)
+        elif self.padding == "causal":
+            x = F.pad(x, ((self.kernel_size - 1) * self.dilation, 0))
+        elif self.padding != "valid":
+            raise ValueError("Padding must be 'same', 'valid' or 'causal'. Got " + self.padding)
+        wx = self.conv(x)
+        if self.unsqueeze:
+            wx = wx.squeeze(1)
+        if not self.skip_transpose:
+            wx = wx.transpose(1, -1)
+        return wx
+
+    def remove_weight_norm(self):
+        self.conv = nn.utils.remove_weight_norm(self.conv)
+        self.weight_norm = False
 
 
 class Conv2d(nn.Module):
