@@ -53,6 +53,32 @@ int sbk_spectrum(int mode, const float* wav, int Bo, int S, int C, int n_fft, in
 /* Number of per-sequence partial-max slots sbk_spectrum(mode 2) writes. */
 int sbk_spectrum_slots(int n_fft, int hop, int T, int M, int n_melw);
 
+/* ISTFT.forward (features.py:273-324, torch.istft) and, as the adjoint of the
+ * analysis transform, the waveform gradient of sbk_spectrum mode 0.
+ * spec: fp32 spectrum addressed as spec[bo*s0 + c*s1 + t*s2 + k*s3 + ri*s4]
+ * with spec_strides a HOST array of 5 int64 (any layout, no copy); bins
+ * 0..n_fft/2 are read (the imaginary parts of DC and Nyquist ignored), and with
+ * fold != 0 conj(spec[n_fft-k]) is added to bin k (two-sided gradient).
+ * out (Bo, L, C): out[l] = sum_t window[s - t*hop] * irfft_t[s - t*hop] at
+ * s = l + start, where irfft_t has bins {0, n_fft/2} weighted scale_edge and the
+ * interior bins scale_int (ISTFT: both 1/n_fft, or n_fft^-1/2 when normalized;
+ * STFT backward: norm_scale and norm_scale/2); divided by sum_t window^2 when
+ * envelope != 0; zeros past the overlap-added signal.  A workgroup owns
+ * sbk_istft_hops(n_fft, hop) hops of the untrimmed axis (0: unsupported);
+ * deterministic (no atomics).  Tables as for sbk_spectrum. */
+int sbk_istft_hops(int n_fft, int hop);
+int sbk_istft(const float* spec, const long long* spec_strides, int Bo, int C, int T, int n_fft, int hop, int fold,
+              float scale_edge, float scale_int, int envelope, int start, int L, const float* window,
+              const float* twiddle_nc, const float* twiddle_nfft, float* out, void* stream);
+
+/* Gradient of sbk_istft (envelope != 0, fold == 0, both scales = scale) with
+ * respect to the spectrum: dy (Bo, L, C) -> dspec through out_strides (as
+ * spec_strides), Fo = n_fft/2+1 or n_fft bins per frame; exact zeros in the
+ * imaginary parts of DC and Nyquist and in the bins above n_fft/2. */
+int sbk_istft_bwd(const float* dy, int Bo, int C, int T, int n_fft, int hop, float scale, int start, int L,
+                  const float* window, const float* twiddle_nc, const float* twiddle_nfft, int Fo,
+                  const long long* out_strides, float* dspec, void* stream);
+
 /* Filterbank.forward on a spectrogram (N, T, F) -> (N, T, M) (features.py:490-560):
  * sparse CSR filters, or a dense (F, M) matrix when `dense` is non-null
  * (learnable filters, freeze=False). */

@@ -30,6 +30,9 @@ SIGNATURES = {
                      _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp],
     "sbk_filterbank": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp],
     "sbk_spectrum_slots": [_i, _i, _i, _i, _i],
+    "sbk_istft_hops": [_i, _i],
+    "sbk_istft": [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "sbk_istft_bwd": [_vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "sbk_filterbank_slots": [_i, _i],
     "sbk_topdb_clamp": [_vp, _vp, _i, _ll, _i, _f, _vp],
     "sbk_filterbank_db_bwd": [_vp, _vp, _i, _ll, _i, _f, _f, _f, _f, _vp, _vp, _vp],

@@ -1870,3 +1870,285 @@ SBK_API int sbk_filterbank_wgrad(const float* spec, const float* dx, long long r
   SBK_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// ISTFT (features.py:191-324, torch.istft) and the STFT / ISTFT gradients.
+//
+// Synthesis (istft_kernel): a workgroup owns HB consecutive hops of the
+// untrimmed overlap-add axis of one (batch, channel) row and transforms the
+// HB + R - 1 frames that overlap them (R = ceil(n_fft / hop)); the R - 1 halo
+// frames are recomputed by the neighbouring workgroup, never exchanged.
+// Per frame: bins k and nc - k are read once and turned straight into the two
+// packed points Z[k], Z[nc - k] of the n_fft/2-point complex transform (the
+// inverse of the forward kernels' real split), stored conjugated so the
+// forward Stockham stages run the inverse; the result is conjugated back,
+// windowed in place and stays in LDS.  Each thread then owns output samples:
+// it sums the <= R frames covering a sample in ascending frame order and the
+// envelope Σ w² in the same loop (no atomics, no envelope tensor; every output
+// written exactly once, zeros past the overlap-added signal).
+// The same kernel is the adjoint of the analysis transform (STFT backward):
+// bin weights ½ on the interior bins, conj(G[n_fft - k]) folded into G[k] for
+// a two-sided gradient, no envelope.
+//
+// Analysis (istft_bwd_kernel): the adjoint of the synthesis.  A workgroup owns
+// FPB frames, stages dy / envelope of their span once, then window -> packed
+// forward FFT -> real split with weights c_k.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct IstftArgs {
+  const float* spec;
+  long long is_b, is_c, is_t, is_k, is_ri;  // spectrum strides (elements): batch, channel, frame, bin, re/im
+  int C, T, n_fft, hop, hb, fold, envelope, start, L;
+  float sc_edge, sc_int;  // weights of bins {0, n_fft/2} and of the interior bins (1/n_fft folded in)
+  const float* window;    // n_fft floats
+  const float2* tw;       // W_nc^m
+  const float2* tw2;      // W_nfft^k, k <= nc
+  float* out;             // (Bo, L, C)
+};
+
+__global__ void __launch_bounds__(256) istft_kernel(IstftArgs a, FftPlan plan) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nc = plan.nc, ncp = frame_stride(nc);
+  const int R = (a.n_fft + a.hop - 1) / a.hop;
+  const int nfmax = a.hb + R - 1;
+  const int ntile = (a.start + a.L + a.hb * a.hop - 1) / (a.hb * a.hop);
+  const int bf = blockIdx.x / ntile;
+  const int h0 = (blockIdx.x - bf * ntile) * a.hb;  // first hop of the tile
+  const int bo = bf / a.C, ch = bf - bo * a.C;
+  const int tA = max(0, h0 - R + 1);                // frames [tA, tB) overlap the tile
+  const int tB = min(a.T, h0 + a.hb);
+  const int nf = max(0, tB - tA);
+
+  float2* bufA = reinterpret_cast<float2*>(smem);
+  float2* bufB = bufA + nfmax * ncp;
+  float2* tw = bufB + nfmax * ncp;
+  float* win = reinterpret_cast<float*>(tw + nc);
+  for (int i = threadIdx.x; i < nc; i += 256) tw[i] = a.tw[i];
+  for (int i = threadIdx.x; i < a.n_fft; i += 256) win[i] = a.window[i];
+
+  // 1) bins k, nc-k -> conj(Z[k]), conj(Z[nc-k]);  Z[k] = (X[k] + X*[nc-k]) + i (X[k] - X*[nc-k]) W*^k
+  const float* srow = a.spec + bo * a.is_b + ch * a.is_c;
+  for_fj(nf, nc / 2 + 1, [&](int f, int k) {
+    const float* p = srow + (long long)(tA + f) * a.is_t;
+    const int k2 = nc - k;
+    float2 A = make_float2(p[k * a.is_k], p[k * a.is_k + a.is_ri]);
+    float2 B = make_float2(p[k2 * a.is_k], p[k2 * a.is_k + a.is_ri]);
+    float sc = a.sc_int;
+    if (k == 0) {  // c2r: the imaginary parts of DC and Nyquist are ignored
+      A.y = 0.f;
+      B.y = 0.f;
+      sc = a.sc_edge;
+    } else if (a.fold) {  // two-sided gradient: X[n_fft-k] = conj(X[k]) carries its share
+      const long long m1 = (long long)(a.n_fft - k) * a.is_k, m2 = (long long)(a.n_fft - k2) * a.is_k;
+      A.x += p[m1];
+      A.y -= p[m1 + a.is_ri];
+      B.x += p[m2];
+      B.y -= p[m2 + a.is_ri];
+    }
+    A = make_float2(A.x * sc, A.y * sc);
+    B = make_float2(B.x * sc, B.y * sc);
+    const float2 w = a.tw2[k];
+    const float2 S = make_float2(A.x + B.x, A.y - B.y), D = make_float2(A.x - B.x, A.y + B.y);
+    const float2 Z1 = cadd(S, mul_pi(cmul(D, make_float2(w.x, -w.y))));
+    bufA[f * ncp + fpad(k)] = make_float2(Z1.x, -Z1.y);
+    if (k > 0 && k2 != k) {  // W*^(nc-k) = -W^k
+      const float2 S2 = make_float2(S.x, -S.y), D2 = make_float2(-D.x, D.y);
+      const float2 Z2 = cadd(S2, mul_pi(cmul(D2, make_float2(-w.x, -w.y))));
+      bufA[f * ncp + fpad(k2)] = make_float2(Z2.x, -Z2.y);
+    }
+  });
+  // 2) forward stages on conj(Z) = conj of the inverse transform
+  float2* Z = run_fft(bufA, bufB, plan, ncp, tw, nf);
+  // 3) conjugate back, window; the frame stays in LDS: sample n at float 2*fpad(n/2) + (n&1)
+  for_fj(nf, nc, [&](int f, int m) {
+    const float2 v = Z[f * ncp + fpad(m)];
+    Z[f * ncp + fpad(m)] = make_float2(v.x * win[2 * m], -v.y * win[2 * m + 1]);
+  });
+  __syncthreads();
+  // 4) overlap-add: one thread per output sample, frames in ascending order
+  const float* fr = reinterpret_cast<const float*>(Z);
+  for_fj(a.hb, a.hop, [&](int h, int r) {
+    const int s = (h0 + h) * a.hop + r, l = s - a.start;
+    if (l < 0 || l >= a.L) return;
+    const int thi = min(h0 + h, a.T - 1);
+    const int tlo = s < a.n_fft ? 0 : (s - a.n_fft) / a.hop + 1;
+    float acc = 0.f, env = 0.f;
+    for (int t = tlo; t <= thi; ++t) {
+      const int n = s - t * a.hop;
+      acc += fr[2 * ((t - tA) * ncp + fpad(n >> 1)) + (n & 1)];
+      env = fmaf(win[n], win[n], env);
+    }
+    if (tlo > thi) acc = 0.f;  // past the overlap-added signal
+    else if (a.envelope) acc /= env;
+    a.out[((long long)bo * a.L + l) * a.C + ch] = acc;
+  });
+}
+
+struct IstftBwdArgs {
+  const float* dy;  // (Bo, L, C)
+  int C, T, n_fft, hop, fpb, start, L, Fo;
+  float scale;      // 1/n_fft (· sqrt(n_fft) when normalized)
+  const float* window;
+  const float2* tw;
+  const float2* tw2;
+  long long os_b, os_c, os_t, os_k, os_ri;
+  float* out;
+};
+
+__global__ void __launch_bounds__(256) istft_bwd_kernel(IstftBwdArgs a, FftPlan plan) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nc = plan.nc, ncp = frame_stride(nc);
+  const int nblk_t = (a.T + a.fpb - 1) / a.fpb;
+  const int bf = blockIdx.x / nblk_t;
+  const int t0 = (blockIdx.x - bf * nblk_t) * a.fpb;
+  const int nf = min(a.fpb, a.T - t0);
+  const int bo = bf / a.C, ch = bf - bo * a.C;
+
+  float2* bufA = reinterpret_cast<float2*>(smem);
+  float2* bufB = bufA + a.fpb * ncp;
+  float2* tw = bufB + a.fpb * ncp;
+  float2* tw2 = tw + nc;
+  float* win = reinterpret_cast<float*>(tw2 + nc + 1);
+  float* g = win + a.n_fft;  // dy / envelope over the tile's span
+  for (int i = threadIdx.x; i < nc; i += 256) tw[i] = a.tw[i];
+  for (int i = threadIdx.x; i <= nc; i += 256) tw2[i] = a.tw2[i];
+  for (int i = threadIdx.x; i < a.n_fft; i += 256) win[i] = a.window[i];
+  __syncthreads();
+  // 1) dy / envelope, zero outside the returned range, shifted by the trim
+  const int s0 = t0 * a.hop, span = (nf - 1) * a.hop + a.n_fft;
+  for (int i = threadIdx.x; i < span; i += 256) {
+    const int s = s0 + i, l = s - a.start;
+    float v = 0.f;
+    if (l >= 0 && l < a.L) {
+      const int thi = min(s / a.hop, a.T - 1);
+      const int tlo = s < a.n_fft ? 0 : (s - a.n_fft) / a.hop + 1;
+      float env = 0.f;
+      for (int t = tlo; t <= thi; ++t) env = fmaf(win[s - t * a.hop], win[s - t * a.hop], env);
+      v = a.dy[((long long)bo * a.L + l) * a.C + ch] / env;
+    }
+    g[i] = v;
+  }
+  __syncthreads();
+  // 2) window, pack two real samples per complex point
+  for_fj(nf, nc, [&](int f, int m) {
+    const int i = f * a.hop + 2 * m;
+    bufA[f * ncp + fpad(m)] = make_float2(g[i] * win[2 * m], g[i + 1] * win[2 * m + 1]);
+  });
+  float2* Z = run_fft(bufA, bufB, plan, ncp, tw, nf);
+  // 3) real split with weights c_k·scale; exact zeros where the forward reads nothing
+  for_fj(nf, a.Fo, [&](int f, int k) {
+    float2 X = make_float2(0.f, 0.f);
+    if (k <= nc) {
+      const float2 zk = Z[f * ncp + fpad(k == nc ? 0 : k)];
+      const float2 zr = Z[f * ncp + fpad(k == 0 ? 0 : nc - k)];
+      const float2 zc = make_float2(zr.x, -zr.y);
+      const float2 E = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
+      const float2 O = mul_mi(make_float2(0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y)));
+      X = cadd(E, cmul(tw2[k], O));
+      const bool edge = k == 0 || k == nc;
+      const float c = edge ? a.scale : 2.f * a.scale;
+      X = make_float2(X.x * c, edge ? 0.f : X.y * c);
+    }
+    float* o = a.out + bo * a.os_b + ch * a.os_c + (long long)(t0 + f) * a.os_t + k * a.os_k;
+    o[0] = X.x;
+    o[a.os_ri] = X.y;
+  });
+}
+
+size_t istft_lds(int n_fft, int nframes) {
+  const int nc = n_fft / 2;
+  return ((size_t)2 * nframes * frame_stride(nc) + nc) * sizeof(float2) + (size_t)n_fft * 4;
+}
+size_t istft_bwd_lds(int n_fft, int hop, int fpb) {
+  const int nc = n_fft / 2;
+  return ((size_t)2 * fpb * frame_stride(nc) + 2 * nc + 1) * sizeof(float2) +
+         ((size_t)2 * n_fft + (size_t)(fpb - 1) * hop) * 4;
+}
+// Hops per synthesis workgroup: as many as keep HB + R - 1 <= 16 frames in
+// 64 KB of LDS; a single hop may take up to 160 KB (opt-in).  0 = refused.
+int istft_hops(int n_fft, int hop) {
+  if (hop <= 0 || !sbk_fft_supported(n_fft)) return 0;
+  const int R = (n_fft + hop - 1) / hop;
+  int hb = std::max(1, 16 - R + 1);
+  while (hb > 1 && istft_lds(n_fft, hb + R - 1) > 64 * 1024) --hb;
+  return istft_lds(n_fft, hb + R - 1) > 160 * 1024 ? 0 : hb;
+}
+int istft_bwd_fpb(int n_fft, int hop) {
+  int fpb = 8;
+  while (fpb > 1 && istft_bwd_lds(n_fft, hop, fpb) > 64 * 1024) fpb >>= 1;
+  return istft_bwd_lds(n_fft, hop, fpb) > 160 * 1024 ? 0 : fpb;
+}
+// frames, hops and the trimmed range must index as int
+bool istft_shape_ok(int Bo, int C, int T, int n_fft, int hop, int start, int L) {
+  if (Bo <= 0 || C <= 0 || T <= 0 || hop <= 0 || start < 0 || L <= 0) return false;
+  const long long lim = 0x7fffffffLL - 2LL * n_fft - 17LL * hop;
+  return (long long)T * hop < lim && (long long)start + L < lim && (long long)Bo * C < 0x7fffffffLL;
+}
+
+}  // namespace
+
+SBK_API int sbk_istft_hops(int n_fft, int hop) { return istft_hops(n_fft, hop); }
+
+// Synthesis: spectrum (strides spec_strides = batch, channel, frame, bin, re/im
+// in elements; bins 0..n_fft/2 read, plus the mirrored bins when fold) ->
+// out (Bo, L, C), out[l] = Σ_t w·irfft(frame t) at s = l + start (÷ Σ w² when envelope).
+SBK_API int sbk_istft(const float* spec, const long long* spec_strides, int Bo, int C, int T, int n_fft, int hop,
+                      int fold, float scale_edge, float scale_int, int envelope, int start, int L,
+                      const float* window, const float* twiddle_nc, const float* twiddle_nfft, float* out,
+                      void* stream) {
+  FftPlan plan;
+  if (n_fft < 4 || (n_fft & 1) || fill_plan(&plan, n_fft / 2)) return SBK_ERR_ARG;
+  if (!istft_shape_ok(Bo, C, T, n_fft, hop, start, L) || !spec || !spec_strides || !out) return SBK_ERR_ARG;
+  const int hb = istft_hops(n_fft, hop);
+  if (!hb) return SBK_ERR_ARG;
+  IstftArgs a;
+  a.spec = spec;
+  a.is_b = spec_strides[0]; a.is_c = spec_strides[1]; a.is_t = spec_strides[2];
+  a.is_k = spec_strides[3]; a.is_ri = spec_strides[4];
+  a.C = C; a.T = T; a.n_fft = n_fft; a.hop = hop; a.hb = hb; a.fold = fold; a.envelope = envelope;
+  a.start = start; a.L = L; a.sc_edge = scale_edge; a.sc_int = scale_int;
+  a.window = window;
+  a.tw = reinterpret_cast<const float2*>(twiddle_nc);
+  a.tw2 = reinterpret_cast<const float2*>(twiddle_nfft);
+  a.out = out;
+  const long long ntile = ((long long)start + L + (long long)hb * hop - 1) / ((long long)hb * hop);
+  const long long nblk = ntile * Bo * C;
+  if (nblk > 0x7fffffffLL) return SBK_ERR_ARG;
+  const size_t lds = istft_lds(n_fft, hb + (n_fft + hop - 1) / hop - 1);
+  if (lds > 64 * 1024)
+    if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&istft_kernel), lds)) return (int)e;
+  hipLaunchKernelGGL(istft_kernel, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, a, plan);
+  SBK_CHECK_LAUNCH();
+  return 0;
+}
+
+// ISTFT backward: dy (Bo, L, C) -> dspec through out_strides (batch, channel,
+// frame, bin, re/im), Fo = n_fft/2 + 1 or n_fft bins per frame.
+SBK_API int sbk_istft_bwd(const float* dy, int Bo, int C, int T, int n_fft, int hop, float scale, int start, int L,
+                          const float* window, const float* twiddle_nc, const float* twiddle_nfft, int Fo,
+                          const long long* out_strides, float* dspec, void* stream) {
+  FftPlan plan;
+  if (n_fft < 4 || (n_fft & 1) || fill_plan(&plan, n_fft / 2)) return SBK_ERR_ARG;
+  if (!istft_shape_ok(Bo, C, T, n_fft, hop, start, L) || !dy || !out_strides || !dspec) return SBK_ERR_ARG;
+  if (Fo != n_fft / 2 + 1 && Fo != n_fft) return SBK_ERR_ARG;
+  const int fpb = istft_bwd_fpb(n_fft, hop);
+  if (!fpb) return SBK_ERR_ARG;
+  IstftBwdArgs a;
+  a.dy = dy; a.C = C; a.T = T; a.n_fft = n_fft; a.hop = hop; a.fpb = fpb; a.start = start; a.L = L; a.Fo = Fo;
+  a.scale = scale;
+  a.window = window;
+  a.tw = reinterpret_cast<const float2*>(twiddle_nc);
+  a.tw2 = reinterpret_cast<const float2*>(twiddle_nfft);
+  a.os_b = out_strides[0]; a.os_c = out_strides[1]; a.os_t = out_strides[2];
+  a.os_k = out_strides[3]; a.os_ri = out_strides[4];
+  a.out = dspec;
+  const long long nblk = (long long)Bo * C * ((T + fpb - 1) / fpb);
+  if (nblk > 0x7fffffffLL) return SBK_ERR_ARG;
+  const size_t lds = istft_bwd_lds(n_fft, hop, fpb);
+  if (lds > 64 * 1024)
+    if (hipError_t e = sbk::lds_optin(reinterpret_cast<const void*>(&istft_bwd_kernel), lds)) return (int)e;
+  hipLaunchKernelGGL(istft_bwd_kernel, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, a, plan);
+  SBK_CHECK_LAUNCH();
+  return 0;
+}

@@ -69,6 +69,138 @@ def _(x, window, tw_nc, tw_nfft, n_fft, hop, center, pad_mode, onesided, normali
     return x.new_empty(x.shape[0], T, Fo, 2)
 
 
+def _spec_strides(t):
+    """(batch, channel, frame, bin, re/im) element strides of a (B,T,F,2) or
+    (B,T,F,2,C) tensor as a host int64 array (kept alive by the caller)."""
+    s = t.stride()
+    return np.array([s[0], s[4] if t.dim() == 5 else 0, s[1], s[2], s[3]], dtype=np.int64)
+
+
+def _overlap_add(spec, window, tw_nc, tw_nfft, n_fft, hop, fold, sc_edge, sc_int, envelope, start, length):
+    """sbk_istft on a spectrum in its own layout (any strides, no copy):
+    (B,T,F,2)->(B,length); (B,T,F,2,C)->(B,length,C)."""
+    require_device(spec, window, tw_nc, tw_nfft)
+    if spec.dim() not in (4, 5) or spec.shape[3] != 2:
+        raise ValueError(f"expected a (B,T,F,2) or (B,T,F,2,C) spectrum, got {tuple(spec.shape)}")
+    spec = spec.to(_f32)
+    B, T = spec.shape[0], spec.shape[1]
+    C = spec.shape[4] if spec.dim() == 5 else 1
+    out = torch.empty((B, length, C) if spec.dim() == 5 else (B, length), device=spec.device, dtype=_f32)
+    st = _spec_strides(spec)
+    rc = _lib.lib().sbk_istft(ptr(spec), st.ctypes.data_as(ctypes.c_void_p), B, C, T, n_fft, hop, int(fold),
+                              sc_edge, sc_int, int(envelope), start, length, ptr(window), ptr(tw_nc), ptr(tw_nfft),
+                              ptr(out), stream_of(spec))
+    check(rc, "sbk_istft")
+    return out
+
+
+def _istft_scale(n_fft, normalized):
+    return (float(n_fft) ** -0.5) if normalized else 1.0 / n_fft
+
+
+@custom_op("sbk::istft", mutates_args=())
+def istft(x: torch.Tensor, window: torch.Tensor, tw_nc: torch.Tensor, tw_nfft: torch.Tensor,
+          n_fft: int, hop: int, center: bool, onesided: bool, normalized: bool, length: int) -> torch.Tensor:
+    """torch.istft on the STFT layout (features.py:273-324): (B,T,F,2)->(B,length),
+    (B,T,F,2,C)->(B,length,C); only bins 0..n_fft/2 are read.  The caller
+    (ISTFT.forward) has checked the window envelope over the returned range."""
+    if x.dim() in (4, 5) and x.shape[2] != (n_fft // 2 + 1 if onesided else n_fft):
+        raise ValueError(f"expected {n_fft // 2 + 1 if onesided else n_fft} bins, got {x.shape[2]}")
+    sc = _istft_scale(n_fft, normalized)
+    return _overlap_add(x, window, tw_nc, tw_nfft, n_fft, hop, False, sc, sc, True,
+                        n_fft // 2 if center else 0, length)
+
+
+@istft.register_fake
+def _(x, window, tw_nc, tw_nfft, n_fft, hop, center, onesided, normalized, length):
+    return x.new_empty((x.shape[0], length, x.shape[4]) if x.dim() == 5 else (x.shape[0], length))
+
+
+@custom_op("sbk::istft_bwd", mutates_args=())
+def istft_bwd(dy: torch.Tensor, window: torch.Tensor, tw_nc: torch.Tensor, tw_nfft: torch.Tensor, T: int, Fo: int,
+              n_fft: int, hop: int, center: bool, normalized: bool) -> torch.Tensor:
+    """Gradient of sbk::istft with respect to the spectrum: dy (B,L) or
+    (B,L,C) -> (B,T,Fo,2[,C]); exact zeros in the imaginary parts of DC and
+    Nyquist and in every bin above n_fft/2."""
+    require_device(dy, window, tw_nc, tw_nfft)
+    dy = _c(dy.to(_f32))
+    B, L = dy.shape[0], dy.shape[1]
+    C = dy.shape[2] if dy.dim() == 3 else 1
+    out = torch.empty((B, T, Fo, 2, C) if dy.dim() == 3 else (B, T, Fo, 2), device=dy.device, dtype=_f32)
+    st = _spec_strides(out)
+    rc = _lib.lib().sbk_istft_bwd(ptr(dy), B, C, T, n_fft, hop, _istft_scale(n_fft, normalized),
+                                  n_fft // 2 if center else 0, L, ptr(window), ptr(tw_nc), ptr(tw_nfft), Fo,
+                                  st.ctypes.data_as(ctypes.c_void_p), ptr(out), stream_of(dy))
+    check(rc, "sbk_istft_bwd")
+    return out
+
+
+@istft_bwd.register_fake
+def _(dy, window, tw_nc, tw_nfft, T, Fo, n_fft, hop, center, normalized):
+    return dy.new_empty((dy.shape[0], T, Fo, 2, dy.shape[2]) if dy.dim() == 3 else (dy.shape[0], T, Fo, 2))
+
+
+def _istft_setup(ctx, inputs, output):
+    x, window, tw_nc, tw_nfft, n_fft, hop, center, onesided, normalized, length = inputs
+    ctx.save_for_backward(window, tw_nc, tw_nfft)
+    ctx.args = (x.shape[1], x.shape[2], n_fft, hop, center, normalized)
+
+
+def _istft_backward(ctx, grad):
+    return (istft_bwd(grad, *ctx.saved_tensors, *ctx.args),) + (None,) * 9
+
+
+istft.register_autograd(_istft_backward, setup_context=_istft_setup)
+
+
+@custom_op("sbk::stft_bwd", mutates_args=())
+def stft_bwd(g: torch.Tensor, window: torch.Tensor, tw_nc: torch.Tensor, tw_nfft: torch.Tensor, S: int,
+             n_fft: int, hop: int, center: bool, pad_mode: int, onesided: bool, normalized: bool) -> torch.Tensor:
+    """Gradient of sbk::stft with respect to the waveform: g (B,T,F,2[,C]) ->
+    (B,S[,C]).  The synthesis kernel in its adjoint role (bin weights ½ on
+    the interior bins, a two-sided gradient folded on load, no envelope)
+    writes the padded axis; the `center` padding (n_fft/2 samples at each
+    end) is folded back with slice ops."""
+    pad = n_fft // 2 if center else 0
+    sc = float(n_fft) ** -0.5 if normalized else 1.0
+    d = _overlap_add(g, window, tw_nc, tw_nfft, n_fft, hop, not onesided, sc, 0.5 * sc, False, 0, S + 2 * pad)
+    if not pad:
+        return d
+    dx = d[:, pad:pad + S].clone()
+    lo, hi = d[:, :pad], d[:, pad + S:]
+    if pad_mode == PAD_MODES["reflect"]:  # padded[i] = x[pad - i]; padded[pad + S + i] = x[S - 2 - i]
+        dx[:, 1:pad + 1] += lo.flip(1)
+        dx[:, S - 1 - pad:S - 1] += hi.flip(1)
+    elif pad_mode == PAD_MODES["replicate"]:
+        dx[:, 0] += lo.sum(1)
+        dx[:, S - 1] += hi.sum(1)
+    elif pad_mode == PAD_MODES["circular"]:  # padded[i] = x[S - pad + i]; padded[pad + S + i] = x[i]
+        dx[:, S - pad:] += lo
+        dx[:, :pad] += hi
+    return dx
+
+
+@stft_bwd.register_fake
+def _(g, window, tw_nc, tw_nfft, S, n_fft, hop, center, pad_mode, onesided, normalized):
+    return g.new_empty((g.shape[0], S, g.shape[4]) if g.dim() == 5 else (g.shape[0], S))
+
+
+def _stft_setup(ctx, inputs, output):
+    x, window, tw_nc, tw_nfft, n_fft, hop, center, pad_mode, onesided, normalized = inputs
+    if center and pad_mode in (PAD_MODES["reflect"], PAD_MODES["circular"]) and \
+            n_fft // 2 > x.shape[1] - (pad_mode == PAD_MODES["reflect"]):
+        raise ValueError("STFT backward: the center padding wraps more than once (n_fft/2 exceeds the signal)")
+    ctx.save_for_backward(window, tw_nc, tw_nfft)
+    ctx.args = (x.shape[1], n_fft, hop, center, pad_mode, onesided, normalized)
+
+
+def _stft_backward(ctx, grad):
+    return (stft_bwd(grad, *ctx.saved_tensors, *ctx.args),) + (None,) * 9
+
+
+stft.register_autograd(_stft_backward, setup_context=_stft_setup)
+
+
 @custom_op("sbk::power_spectrum", mutates_args=())
 def power_spectrum(x: torch.Tensor, window: torch.Tensor, tw_nc: torch.Tensor, tw_nfft: torch.Tensor,
                    n_fft: int, hop: int, center: bool, pad_mode: int, normalized: bool,

@@ -1,4 +1,4 @@
-"""Drop-in for speechbrain.processing.features (STFT, spectral_magnitude,
+"""Drop-in for speechbrain.processing.features (STFT, ISTFT, spectral_magnitude,
 Filterbank, DCT, Deltas, ContextWindow) on HIP kernels.
 
 Constructor arguments, attributes, buffers (state_dict keys) and forward
@@ -15,7 +15,7 @@ from .._lib import check as _check, lib as _lib, ptr as _ptr, require_device as 
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["STFT", "spectral_magnitude", "Filterbank", "DCT", "Deltas", "ContextWindow", "InputNormalization"]
+__all__ = ["STFT", "ISTFT", "spectral_magnitude", "Filterbank", "DCT", "Deltas", "ContextWindow", "InputNormalization"]
 
 
 class _DevCache:
@@ -91,6 +91,74 @@ class STFT(torch.nn.Module):
         return ops.power_spectrum(x, w, tw1, tw2, self.n_fft, self.hop_length, self.center,
                                   ops.PAD_MODES[self.pad_mode], self.normalized_stft,
                                   float(power), float(eps), bool(log))
+
+
+class ISTFT(torch.nn.Module):
+    """Inverse Short-Term Fourier Transform (features.py:191-324): inverse
+    real FFT, window, overlap-add and envelope division in one kernel
+    (sbk_istft); (B,T,F,2)→(B,L), (B,T,F,2,C)→(B,L,C), differentiable with
+    respect to the spectrum.  ISTFT(16000)(STFT(16000)(x)) returns x's shape
+    for x of (10, 16000).  normalized_stft is honoured (the inverse of
+    STFT(normalized_stft=True)); the reference accepts the flag but never
+    passes it to torch.istft."""
+
+    def __init__(self, sample_rate, n_fft=None, win_length=25, hop_length=10, window_fn=torch.hamming_window,
+                 normalized_stft=False, center=True, onesided=True, epsilon=1e-12):
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.n_fft = n_fft
+        self.normalized_stft = normalized_stft
+        self.center = center
+        self.onesided = onesided
+        self.epsilon = epsilon
+        self.win_length = int(round((self.sample_rate / 1000.0) * win_length))
+        self.hop_length = int(round((self.sample_rate / 1000.0) * hop_length))
+        self.window = window_fn(self.win_length)
+        self._cache = _DevCache()
+        self._env_ok = {}
+
+    def _padded_window(self, n_fft):
+        w = torch.zeros(n_fft, dtype=torch.float32)
+        left = (n_fft - self.win_length) // 2
+        w[left:left + self.win_length] = self.window.to(torch.float32)
+        return w
+
+    def _check_envelope(self, n_fft, T, start, end):
+        """torch.istft's "window overlap add min" check over the returned
+        range [start, end) of the overlap-added axis, from the host window
+        (no device sync), cached per (n_fft, T, range)."""
+        key = (n_fft, T, start, end)
+        ok = self._env_ok.get(key)
+        if ok is None:
+            w2 = self._padded_window(n_fft).double().square()
+            env = torch.nn.functional.fold(w2.view(1, n_fft, 1).repeat(1, 1, T), (1, (T - 1) * self.hop_length + n_fft),
+                                           (1, n_fft), stride=(1, self.hop_length)).flatten()[start:end]
+            ok = self._env_ok[key] = bool(env.numel() > 0 and env.abs().min() >= 1e-11)
+        if not ok:
+            raise RuntimeError("istft(window overlap add min: 1): the window envelope is (nearly) zero inside the "
+                               "returned range")
+
+    def forward(self, x, sig_length=None):
+        """Returns the ISTFT of a batch of spectra (features.py:273-324)."""
+        _require_device(x)
+        if self.n_fft is None:
+            n_fft = (x.shape[2] - 1) * 2 if self.onesided else x.shape[2]
+        else:
+            n_fft = self.n_fft
+        if n_fft < self.win_length:
+            raise ValueError(f"win_length {self.win_length} exceeds n_fft {n_fft}")
+        if not _lib().sbk_fft_supported(n_fft):
+            raise ValueError(f"n_fft {n_fft} does not factor into the FFT radices 8/5/4/3/2")
+        T, hop = x.shape[1], self.hop_length
+        full = (T - 1) * hop + n_fft
+        start = n_fft // 2 if self.center else 0
+        length = int(sig_length) if sig_length is not None else full - 2 * start
+        self._check_envelope(n_fft, T, start, min(start + length, full))
+
+        def make():
+            return (self._padded_window(n_fft),) + fft_twiddles(n_fft)
+        w, tw1, tw2 = self._cache.get(("istft", n_fft), x.device, make)
+        return ops.istft(x, w, tw1, tw2, n_fft, hop, self.center, self.onesided, self.normalized_stft, length)
 
 
 def spectral_magnitude(stft, power=1, log=False, eps=1e-14):
